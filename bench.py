@@ -22,6 +22,12 @@ themselves instead (one all-to-all per micro-batch before a single-phase operato
 Roofline: HBM. Algorithmic bytes: 24 B per input record + 48 B per fired
 row. `roofline` is for the dominant kernel, timed with HIP events on the engine's
 stream; `job_roofline_frac` is the whole-job B_alg / t / (N * 8 TB/s).
+
+A plain run sets up, warms up, times `--steps` steps and prints the result line
+(`ms_per_step`: wall milliseconds of one timed step). `--dump-outputs DIR` also writes the
+rows the last timed step fired (OutputSample). `--full` adds the secondary legs, each a run
+of its own after the timed steps: the CPU baseline (`cpu_baseline`), the pinned-host H2D
+leg (`h2d`) and the device copy peak (`roofline.copy_peak_gbs`).
 """
 from __future__ import annotations
 
@@ -281,6 +287,96 @@ class TwoPhase:
         return a + b, sent
 
 
+DUMP_BUDGET = 48 << 20   # bytes of --dump-outputs arrays (the files stay under 64 MB)
+DUMP_HASH = s64(0x9E3779B97F4A7C15)
+
+
+class OutputSample:
+    """--dump-outputs: the fired rows of one step (the device FgRows a caller of the timed path
+    receives from collect_fired / process_watermark), kept as they are collected -- the engine
+    reuses their buffers at the next fire. A step fires up to `max_rows` rows (4.8 GB on
+    configs[1]), so the rows of a fixed, seeded sample of the KEYS are kept: those whose
+    multiplicative hash of the key falls under 2^-shift of its range, the largest such fraction
+    that holds `max_rows` rows in DUMP_BUDGET (every row when they all fit). The choice depends
+    on the arguments alone, and the rows are written sorted by (window_end, window_start, key):
+    two builds write the same rows in the same order whatever order their fires emit them in."""
+
+    def __init__(self, op, max_rows, device):
+        from flink_amd import _lib as FL
+        from flink_amd.window_agg import AGG_NAMES, VALUE_TYPED
+        self.device = device
+        self.names = ["key", "window_start", "window_end"] + (["rowtime"] if op.mode == FL.MODE_DATASTREAM else [])
+        self.aggs = [(AGG_NAMES[a], op.val_type == FL.VAL_F64 and a in VALUE_TYPED) for a in op.aggs]
+        row_bytes = 8 * (len(self.names) + len(self.aggs))
+        self.shift = 0
+        while self.shift < 40 and (max_rows >> self.shift) * row_bytes > DUMP_BUDGET:
+            self.shift += 1
+        self.parts = []
+        # the copies run on a stream of their own beside the engine's queued work, and the host
+        # does not wait for them (the timed step pays their launches only)
+        self.side = torch.cuda.Stream(device)
+        self.engine = torch.cuda.ExternalStream(op.stream, device=device)
+
+    def take(self, r):
+        """keep the sampled rows of the device FgRows `r` (complete: the host has waited for their
+        fire); returns r.n. The engine's stream is made to wait for the copies, so the operator's
+        next fire reuses the buffers of `r` after them."""
+        n = int(r.n)
+        if n == 0:
+            return 0
+        from flink_amd.exchange import device_columns
+        with torch.cuda.stream(self.side):
+            cols = device_columns(r, names=self.names, aggs=tuple(range(len(self.aggs))), device=self.device)
+            nullm = torch.as_tensor(_U8Column(r.null_mask, n), device=self.device)
+            if self.shift:
+                # no host round trip for the count: room for twice the expected rows, the rows
+                # kept counted on the device and checked in write()
+                keep = lsr(cols[0] * DUMP_HASH, 24) < (1 << (40 - self.shift))
+                idx = torch.nonzero_static(keep, size=2 * (n >> self.shift) + 4096, fill_value=0).squeeze(1)
+                kept = keep.sum()
+                cols = [c[idx] for c in cols]
+                nullm = nullm[idx]
+            else:
+                kept = None
+                cols = [c.clone() for c in cols]
+                nullm = nullm.clone()
+        self.parts.append((cols, nullm, kept))
+        self.engine.wait_stream(self.side)
+        return n
+
+    def write(self, path):
+        """DIR/<column>.npy, float64 (keys, timestamps and counts are below 2^53: exact); an
+        aggregate that is NULL in a row (its null_mask bit) is written as NaN."""
+        os.makedirs(path, exist_ok=True)
+        torch.cuda.synchronize()
+        ncol = len(self.names) + len(self.aggs)
+        kept = [len(p[1]) if p[2] is None else int(p[2]) for p in self.parts]
+        if any(k > len(p[1]) for k, p in zip(kept, self.parts)):
+            raise RuntimeError("--dump-outputs: a fire's sampled rows exceed twice their expected number")
+        cols = [np.concatenate([p[0][i][:k].cpu().numpy() for k, p in zip(kept, self.parts)]) if self.parts else
+                np.zeros(0, np.int64) for i in range(ncol)]
+        nullm = (np.concatenate([p[1][:k].cpu().numpy() for k, p in zip(kept, self.parts)]) if self.parts else
+                 np.zeros(0, np.uint8))
+        order = np.lexsort((cols[0], cols[1], cols[2]))
+        for nm, c in zip(self.names, cols):
+            np.save(os.path.join(path, nm + ".npy"), c[order].astype(np.float64))
+        for i, (nm, is_f) in enumerate(self.aggs):
+            c = cols[len(self.names) + i][order]
+            c = c.view(np.float64).copy() if is_f else c.astype(np.float64)
+            c[(nullm[order] >> i) & 1 == 1] = np.nan
+            np.save(os.path.join(path, nm + ".npy"), c)
+        return {"dir": path, "rows": int(len(order)), "key_fraction": 2.0 ** -self.shift,
+                "columns": self.names + [nm for nm, _ in self.aggs]}
+
+
+class _U8Column:
+    """Zero-copy view of an engine-owned device byte column (FgRows.null_mask) for torch.as_tensor."""
+
+    def __init__(self, ptr, n):
+        self.__cuda_array_interface__ = {"shape": (n,), "typestr": "|u1", "data": (int(ptr or 0), False),
+                                         "version": 2}
+
+
 def measure_copy_peak(dev, nbytes=2 << 30, reps=5):
     """Device-to-device copy bandwidth (read + write bytes / time) on this GPU."""
     try:
@@ -534,7 +630,14 @@ def main():
                          "(beside pass 1) or after its watermarks (beside the fires)")
     ap.add_argument("--intern-serial", action="store_true",
                     help="strings: intern the next micro-batch after the engine's passes instead of beside them (A/B)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the secondary legs, each a run of its own: the CPU "
+                         "baseline (oracle), the pinned-host H2D leg and the device copy peak of the roofline "
+                         "(default: only the timed steps; their fields are null or absent)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the rows the last timed step fired as DIR/<column>.npy (float64, sorted by "
+                         "window and key; at most 64 MB: a fixed sample of the keys of a larger output)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--cpu-max-records", type=int, default=200_000_000)
     ap.add_argument("--host-input", action="store_true",
@@ -545,8 +648,11 @@ def main():
                     help="CPU baseline instances (default: min(85, CPUs in this process's affinity mask))")
     ap.add_argument("--h2d-records", type=int, default=1_000_000_000,
                     help="records of the pinned-host leg (SURVEY 8(d) contract timing: FG_HOST batches, "
-                         "double-buffered H2D overlapping the kernels); 0 skips it. Never the headline value")
+                         "double-buffered H2D overlapping the kernels) under --full; 0 skips it. Never the "
+                         "headline value")
     args = ap.parse_args()
+    if args.dump_outputs and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        ap.error("--dump-outputs writes the rows of a one-GPU run")
     wl = dict(WORKLOADS[args.workload])
     if args.jitter is not None:
         wl["jitter"] = wl["delay"] = args.jitter
@@ -708,7 +814,9 @@ def main():
         k, _ = kdict.intern_async((rows_u8[32 * lo:32 * hi], row_off[:hi - lo], row_len[:hi - lo]))
         return k
 
-    def one_step():
+    def one_step(sample=None):
+        """one job; sample (an OutputSample): keeps the rows of every fire as they are collected"""
+        take = sample.take if sample else (lambda r: r.n)
         op.reset()
         rows0 = op.stats()["rows_fired"]
         if op_local:
@@ -726,7 +834,7 @@ def main():
         for bi, lo in enumerate(range(0, n, args.batch)):
             if args.checkpoint_every and bi > 0 and bi % args.checkpoint_every == 0:
                 if held and tp is None:   # the rows go out before the checkpoint barrier
-                    rows += op.collect_fired().n
+                    rows += take(op.collect_fired())
                     held = False
                 nr, sent = checkpoint()
                 rows += nr
@@ -757,13 +865,13 @@ def main():
                 torch.cuda.current_stream().synchronize()
             op.process_batch(k, t, v)
             if held:   # the previous batch's watermarks: their rows, then (a shim) the watermarks go on
-                rows += op.collect_fired().n
+                rows += take(op.collect_fired())
                 held = False
             if world > 1 and wms:
                 wms[-1] = global_watermark(wms[-1], device=dev)
             if args.wm_sync:
                 for wm in wms:
-                    rows += op.process_watermark(wm, device_output=True).n
+                    rows += take(op.process_watermark(wm, device_output=True))
             elif wms:   # fg_advance_progress_async_n: every watermark's fires queued, the watermarks held
                 op.process_watermarks(wms)
                 held = True
@@ -784,9 +892,8 @@ def main():
             nr, sent = tp.finish()
             return rows + nr, xgmi + sent
         if held:
-            rows += op.collect_fired().n
-        r = op.process_watermark(JMAX, device_output=True)
-        rows += r.n
+            rows += take(op.collect_fired())
+        rows += take(op.process_watermark(JMAX, device_output=True))
         assert args.wm_sync or rows == op.stats()["rows_fired"] - rows0
         return rows, xgmi
 
@@ -799,12 +906,19 @@ def main():
             ks.update(kdict.kernel_stats())
         return ks
 
+    sample = None
+    if args.dump_outputs:   # (a record is in size / slide windows of a HOP, at most as many of a CUMULATE)
+        sample = OutputSample(op, n * (-(-window.size // window.slide) if window.slide else 1), dev)
     pre_last = kstats()
     for i in range(args.warmup):
         if i == args.warmup - 1:
             op.synchronize()
             pre_last = kstats()
-        one_step()
+        # (the last warmup step keeps its rows too, then drops them: the copies' kernels are
+        # loaded and their memory allocated before the timed steps)
+        one_step(sample if i == args.warmup - 1 else None)
+    if sample is not None:
+        sample.parts.clear()
     snapshot_collect()
     op.synchronize()
     # every kernel class is timed in the warmup; the timed region brackets only the dominant
@@ -834,8 +948,8 @@ def main():
     t0 = time.perf_counter()
     tot_rows = 0
     tot_xgmi = 0
-    for _ in range(args.steps):
-        rows, xg = one_step()
+    for i in range(args.steps):
+        rows, xg = one_step(sample if i == args.steps - 1 else None)
         tot_rows += rows
         tot_xgmi += xg
     # the last checkpoint's image (each earlier one was collected by the next checkpoint: the async
@@ -874,7 +988,7 @@ def main():
     achieved = alg_bytes / avg_s / 1e9
     traffic, traffic_src = pmc_traffic(dom_name, args.workload)
 
-    copy_gbs = measure_copy_peak(dev)
+    copy_gbs = measure_copy_peak(dev) if args.full else None
     total_records = world * n * args.steps
     value = total_records / el
     b_alg = 24 * total_records + 48 * tot_rows
@@ -928,14 +1042,18 @@ def main():
         "kernels_warmup": {k: dict(v, avg_ms=v["total_ms"] / v["launches"]) for k, v in warm.items()},
         "cpu_baseline": None,
     }
-    if rank == 0 and world == 1 and args.h2d_records > 0 and not args.host_input and args.workload == "tumble":
+    if sample is not None:
+        result["outputs"] = sample.write(args.dump_outputs)
+        del sample
+    if (args.full and rank == 0 and world == 1 and args.h2d_records > 0 and not args.host_input
+            and args.workload == "tumble"):
         # secondary: the same workload handed over as pinned host columns (the FG_HOST
         # boundary a JNI shim uses), H2D double-buffered on the engine's copy stream
         op.close()
         del key, ts, val
         torch.cuda.empty_cache()
         result["h2d"] = h2d_leg(args, wl, window, aggs, expected_keys, dev)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             result["cpu_baseline"] = cpu_baseline(args, args.rate // 1000)
         except Exception as e:  # reported, not fatal
