@@ -101,6 +101,10 @@ class FgStats(C.Structure):
         "state_regions", "region_capacity")]
 
 
+class FgRestoreInfo(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("rows_in", "rows_kept", "slices", "state_regions")]
+
+
 class FgKernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("launches", C.c_int64), ("total_ms", C.c_double),
                 ("records", C.c_int64), ("rows", C.c_int64)]
@@ -118,7 +122,7 @@ EXPORTS = (
     "fg_open", "fg_add_batch", "fg_add_rows", "fg_add_partials", "fg_advance_progress", "fg_advance_progress_async",
     "fg_advance_progress_async_n",
     "fg_collect_fired", "fg_collect_fired_to", "fg_flush", "fg_flush_partials", "fg_snapshot_state",
-    "fg_snapshot_state_async", "fg_snapshot_state_wait", "fg_snapshot_slices", "fg_selftest", "fg_restore", "fg_late_dropped", "fg_get_stats", "fg_synchronize", "fg_reset", "fg_kernel_stats", "fg_set_kernel_timing",
+    "fg_snapshot_state_async", "fg_snapshot_state_wait", "fg_snapshot_slices", "fg_selftest", "fg_restore", "fg_restore_range", "fg_late_dropped", "fg_get_stats", "fg_synchronize", "fg_reset", "fg_kernel_stats", "fg_set_kernel_timing",
     "fg_stream",
     "fg_last_error", "fg_close", "fg_key_groups", "fg_partition_by_owner", "fg_partition_columns_by_owner",
     "fg_abi_version", "fg_key_dict_open", "fg_key_dict_intern", "fg_key_dict_intern_async",
@@ -175,6 +179,8 @@ def load():
     L.fg_snapshot_state_async.argtypes = [P]
     L.fg_snapshot_state_wait.argtypes = [P, C.POINTER(FgStateRows), C.POINTER(C.c_int64)]
     L.fg_restore.argtypes = [P, C.POINTER(FgStateRows), C.c_int64]
+    L.fg_restore_range.argtypes = [P, C.POINTER(FgStateRows), C.c_int32, C.c_int32, C.c_int32, C.c_int64,
+                                   C.POINTER(FgRestoreInfo)]
     L.fg_late_dropped.argtypes = [P, C.POINTER(C.c_int64)]
     L.fg_get_stats.argtypes = [P, C.POINTER(FgStats)]
     L.fg_synchronize.argtypes = [P]
@@ -250,7 +256,7 @@ def load():
         getattr(L, fn).restype = C.c_int
     for fn in ("fg_open", "fg_add_batch", "fg_add_rows", "fg_add_partials", "fg_advance_progress",
                "fg_advance_progress_async", "fg_advance_progress_async_n", "fg_collect_fired", "fg_collect_fired_to", "fg_flush", "fg_flush_partials",
-               "fg_snapshot_state", "fg_snapshot_state_async", "fg_snapshot_state_wait", "fg_snapshot_slices", "fg_restore", "fg_late_dropped", "fg_get_stats", "fg_synchronize", "fg_reset", "fg_kernel_stats", "fg_key_groups",
+               "fg_snapshot_state", "fg_snapshot_state_async", "fg_snapshot_state_wait", "fg_snapshot_slices", "fg_restore", "fg_restore_range", "fg_late_dropped", "fg_get_stats", "fg_synchronize", "fg_reset", "fg_kernel_stats", "fg_key_groups",
                "fg_partition_by_owner", "fg_partition_columns_by_owner"):
         getattr(L, fn).restype = C.c_int
     _lib = L

@@ -174,11 +174,13 @@ constexpr int64_t kHeavyMin = 1 << 16;
 constexpr int64_t kHeavyChunk = 1 << 16;
 
 enum KClass { K_COUNT = 0, K_SCAN, K_SCATTER, K_PART1, K_PART2, K_FLUSH, K_FLUSH_FIRE, K_FIRE, K_EXPORT, K_RESTORE,
-              K_HEAVY, K_TILE1, K_TILE_FIRE, K_TILE_MAT, K_TILE_FLUSH, K_TILE_SPLIT, K_NCLASS };
+              K_HEAVY, K_TILE1, K_TILE_FIRE, K_TILE_MAT, K_TILE_FLUSH, K_TILE_SPLIT, K_RR_FILTER, K_RR_SCATTER,
+              K_NCLASS };
 const char* const kClassName[K_NCLASS] = {"ingest_count", "ingest_scan",      "ingest_scatter", "ingest_part1",
                                            "ingest_part2", "merge_flush",      "merge_flush_fire", "merge_fire",
                                            "export",       "restore",          "merge_heavy",      "tile_part1",
-                                           "tile_fire",    "tile_materialize", "tile_flush",       "tile_split_fire"};
+                                           "tile_fire",    "tile_materialize", "tile_flush",       "tile_split_fire",
+                                           "restore_filter", "restore_scatter"};
 struct KStat {
     int64_t launches = 0;
     double ms = 0;
@@ -4353,6 +4355,8 @@ int fg_snapshot_state(fg_handle* h, fg_state_rows* out, int64_t* timer_watermark
     return snapshot_end(h, out, timer_watermark);
 }
 
+static int restore_finish(fg_handle* h, int64_t timer_watermark, bool was_empty);
+
 int fg_restore(fg_handle* h, const fg_state_rows* in, int64_t timer_watermark) {
     if (!h || !in) return FG_EINVAL;
     const bool was_empty = h->tables.empty();   // (restored into a new handle: its tables equal the image)
@@ -4472,6 +4476,12 @@ int fg_restore(fg_handle* h, const fg_state_rows* in, int64_t timer_watermark) {
         t->upper = std::min<int64_t>(t->upper + m, kStateCapMax);
         t->changed = true;
     }
+    return restore_finish(h, timer_watermark, was_empty);
+}
+
+// What a restore leaves besides the slice tables (fg_restore, fg_restore_range): progress, timer
+// watermark, re-fire and lateness horizons, the `changed` flags.
+static int restore_finish(fg_handle* h, int64_t timer_watermark, bool was_empty) {
     // open(): processor progress restarts at Long.MIN_VALUE, and so does the restored timer
     // service's watermark (InternalTimerServiceImpl.currentWatermark is not part of the
     // snapshot): a record older than the checkpoint's watermark is not late, its flush
@@ -4508,6 +4518,238 @@ int fg_restore(fg_handle* h, const fg_state_rows* in, int64_t timer_watermark) {
     // write reaches it (the shim's next checkpoint rewrites only the slices that change)
     if (was_empty)
         for (auto& kv : h->tables) kv.second->changed = false;
+    return FG_OK;
+}
+
+// The rows of fg_restore_range's images that fall into the handle's key-group range, merged into
+// the slice tables: the filter, the grouping by (slice, region) and the scatter are kernels
+// (fg_kernels.h, k_rr_*); the host reads the slice dictionary and per-slice sizes, never a row.
+static int restore_range_rows(fg_handle* h, const fg_state_rows* images, int32_t n_images, int32_t location,
+                              int32_t key_hash, int64_t N, fg_restore_info* ri) {
+    const int ncols = h->mv ? 7 : 5;
+    std::vector<RrImage> desc;
+    DevBuf up;   // FG_HOST: the images' columns, one after the other over the concatenated rows
+    if (location == FG_HOST) {
+        HIPCHK(h, up.ensure(8 * (size_t)N * ncols));
+        int64_t* base = up.as<int64_t>();
+        int64_t first = 0;
+        for (int32_t g = 0; g < n_images; g++) {
+            const fg_state_rows& im = images[g];
+            if (im.n == 0) continue;
+            const int64_t* src[7] = {im.key, im.slice_end, im.cnt_star, im.cnt_val, im.sum, im.min, im.max};
+            for (int c = 0; c < ncols; c++)
+                HIPCHK(h, hipMemcpyAsync(base + (int64_t)c * N + first, src[c], 8 * (size_t)im.n, hipMemcpyHostToDevice,
+                                         h->stream));
+            first += im.n;
+        }
+        desc.push_back(RrImage{base, base + N, base + 2 * N, base + 3 * N, base + 4 * N, h->mv ? base + 5 * N : nullptr,
+                               h->mv ? base + 6 * N : nullptr, 0, N});
+    } else {
+        int64_t first = 0;
+        for (int32_t g = 0; g < n_images; g++) {
+            const fg_state_rows& im = images[g];
+            if (im.n == 0) continue;
+            desc.push_back(RrImage{im.key, im.slice_end, im.cnt_star, im.cnt_val, im.sum, h->mv ? im.min : nullptr,
+                                   h->mv ? im.max : nullptr, first, im.n});
+            first += im.n;
+        }
+    }
+    DevBuf d_img, d_dict;
+    HIPCHK(h, d_img.ensure(sizeof(RrImage) * desc.size()));
+    HIPCHK(h, hipMemcpyAsync(d_img.p, desc.data(), sizeof(RrImage) * desc.size(), hipMemcpyHostToDevice, h->stream));
+    const size_t dict_bytes = 8 * (size_t)kRrDictSlots + 16;
+    HIPCHK(h, d_dict.ensure(dict_bytes));
+    HIPCHK(h, hipMemsetAsync(d_dict.p, 0xFF, 8 * (size_t)kRrDictSlots, h->stream));
+    HIPCHK(h, hipMemsetAsync(d_dict.as<char>() + 8 * (size_t)kRrDictSlots, 0, 16, h->stream));
+    RrParams p{};
+    p.img = d_img.as<RrImage>();
+    p.n_images = (int32_t)desc.size();
+    p.grid = rr_grid(N);
+    p.n = N;
+    p.key_hash = key_hash;
+    p.max_p = h->cfg.max_parallelism;
+    p.kg_lo = h->cfg.key_group_start;
+    p.kg_hi = h->cfg.key_group_end;
+    p.dict = d_dict.as<unsigned long long>();
+    p.dict_n = reinterpret_cast<uint32_t*>(d_dict.as<unsigned long long>() + kRrDictSlots);
+    {
+        KTimer kt(h, K_RR_FILTER, N);
+        HIPCHK(h, launch_rr_dict(p, h->stream));
+    }
+    std::vector<unsigned long long> hd(kRrDictSlots + 2);
+    HIPCHK(h, hipMemcpyAsync(hd.data(), d_dict.p, dict_bytes, hipMemcpyDeviceToHost, h->stream));
+    int rc = sync(h);
+    if (rc) return rc;
+    uint32_t dn[4];
+    std::memcpy(dn, &hd[kRrDictSlots], sizeof dn);
+    if ((int64_t)dn[0] + (dn[1] ? 1 : 0) > kRrMaxSlices)
+        return h->fail(FG_EINVAL, "fg_restore_range: more than %d distinct slice ends in one call", kRrMaxSlices);
+    std::vector<int64_t> slices;
+    for (int i = 0; i < kRrDictSlots; i++)
+        if (hd[i] != kRrDictEmpty) slices.push_back((int64_t)hd[i]);
+    if (dn[1]) slices.push_back((int64_t)kRrDictEmpty);
+    std::sort(slices.begin(), slices.end());
+    const int32_t S = (int32_t)slices.size();
+    if (S < 1 || S > kRrMaxSlices) return h->fail(FG_EDEVICE, "internal: fg_restore_range slice dictionary of %d", S);
+    // kept rows per (slice, 13 region bits), and from them the fullest region of every split
+    DevBuf d_sl, d_hist, d_size;
+    HIPCHK(h, d_sl.ensure(8 * (size_t)S));
+    HIPCHK(h, d_hist.ensure(4 * (size_t)S * kRrHist));
+    HIPCHK(h, d_size.ensure(4 * (size_t)S * kRrSizeCols));
+    HIPCHK(h, hipMemcpyAsync(d_sl.p, slices.data(), 8 * (size_t)S, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(d_hist.p, 0, 4 * (size_t)S * kRrHist, h->stream));
+    p.slices = d_sl.as<int64_t>();
+    p.n_slices = S;
+    p.hist = d_hist.as<uint32_t>();
+    {
+        KTimer kt(h, K_RR_FILTER, N);
+        HIPCHK(h, launch_rr_count(p, h->stream));
+        HIPCHK(h, launch_rr_size(p.hist, S, d_size.as<uint32_t>(), h->stream));
+    }
+    std::vector<uint32_t> sz((size_t)S * kRrSizeCols);
+    HIPCHK(h, hipMemcpyAsync(sz.data(), d_size.p, 4 * sz.size(), hipMemcpyDeviceToHost, h->stream));
+    rc = sync(h);
+    if (rc) return rc;
+    // regions sized for the kept rows by fg_restore's rule: the smallest split whose fullest
+    // region keeps the LDS tables at most ~70 % full
+    int need = h->region_bits;
+    int64_t kept = 0, live = 0;
+    for (int32_t s = 0; s < S; s++) {
+        const uint32_t* m = &sz[(size_t)s * kRrSizeCols];
+        if (m[0] == 0) continue;   // every row of the slice is foreign
+        kept += m[0];
+        live++;
+        for (int b = need; b <= kMaxRegionBits; b++) {
+            need = b;
+            if (m[b] <= (uint32_t)(0.7 * h->tcap)) break;
+        }
+    }
+    ri->rows_kept = kept;
+    ri->slices = live;
+    rc = grow(h, need);
+    if (rc) return rc;
+    if (kept == 0) return FG_OK;
+    // (slice, region) offsets at the handle's split, then the kept rows grouped by them
+    const int bits = h->region_bits;
+    const int64_t NB = (int64_t)1 << bits;
+    const int64_t F = (int64_t)S * NB;
+    const int vcols = h->mv ? 6 : 4;
+    DevBuf d_cnt, d_off, d_tmp, d_cur, d_out;
+    HIPCHK(h, d_cnt.ensure(4 * (size_t)F));
+    HIPCHK(h, d_off.ensure(4 * (size_t)(F + 1)));
+    HIPCHK(h, d_tmp.ensure(4 * scan_tmp_words(F)));
+    HIPCHK(h, d_cur.ensure(4 * (size_t)F));
+    HIPCHK(h, d_out.ensure(8 * (size_t)kept * vcols));
+    int64_t* ob = d_out.as<int64_t>();
+    p.region_bits = bits;
+    p.cursor = d_cur.as<uint32_t>();
+    p.o_cap = kept;
+    p.o_key = ob;
+    p.o_cs = ob + kept;
+    p.o_cn = ob + 2 * kept;
+    p.o_sum = ob + 3 * kept;
+    p.o_v1 = h->mv ? ob + 4 * kept : nullptr;
+    p.o_v2 = h->mv ? ob + 5 * kept : nullptr;
+    {
+        KTimer kt(h, K_RR_SCATTER, kept);
+        HIPCHK(h, launch_rr_fold(p.hist, S, bits, d_cnt.as<uint32_t>(), h->stream));
+        HIPCHK(h, launch_scan_u32(d_cnt.as<uint32_t>(), d_off.as<uint32_t>(), F, d_tmp.as<uint32_t>(), h->stream));
+        HIPCHK(h, hipMemcpyAsync(d_cur.p, d_off.p, 4 * (size_t)F, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(h, launch_rr_scatter(p, h->stream));
+    }
+    // one K_RESTORE merge per slice over its segment of the batch (which lives until the last
+    // settle_jobs below)
+    int64_t at = 0;
+    for (int32_t s = 0; s < S; s++) {
+        const int64_t m = sz[(size_t)s * kRrSizeCols];
+        if (m == 0) continue;
+        SliceTable* t = nullptr;
+        rc = table_get(h, slices[s], true, &t);
+        if (rc) return rc;
+        MergeJob j;
+        JobBatch jb;
+        jb.ext.rec = p.o_key + at;
+        jb.ext.stride = 1;
+        jb.ext.val = p.o_sum + at;
+        jb.ext.cnt_star = p.o_cs + at;
+        jb.ext.cnt_null = p.o_cn + at;
+        jb.ext.bucket_off = d_off.as<uint32_t>() + (int64_t)s * NB;
+        jb.ext.is_acc = 1;
+        jb.ext.val1 = h->mv ? p.o_v1 + at : nullptr;
+        jb.ext.val2 = h->mv ? p.o_v2 + at : nullptr;
+        jb.ext_bits = bits;
+        j.batches.push_back(jb);
+        j.srcs.push_back(t);
+        j.dst = t;
+        j.kclass = K_RESTORE;
+        if (int rc0 = zero_scalars(h, true)) return rc0;
+        int ji = 0;
+        rc = job_add(h, std::move(j), &ji);
+        if (rc) return rc;
+        MergeParams mp{};
+        rc = job_params(h, ji, &mp);
+        if (rc) return rc;
+        {
+            KTimer kt(h, K_RESTORE, m);
+            HIPCHK(h, launch_merge(mp, merge_grid(h), h->stream));
+        }
+        HIPCHK(h, hipMemcpyAsync(h->h_scalars.p, h->scalars.p, kScalarBytes, hipMemcpyDeviceToHost, h->stream));
+        rc = sync(h);
+        if (rc) return rc;
+        rc = settle_jobs(h);
+        if (rc) return rc;
+        rc = check_overflow(h);
+        if (rc) return rc;
+        t->upper = std::min<int64_t>(t->upper + m, kStateCapMax);
+        t->changed = true;
+        at += m;
+    }
+    return FG_OK;
+}
+
+int fg_restore_range(fg_handle* h, const fg_state_rows* images, int32_t n_images, int32_t location, int32_t key_hash,
+                     int64_t timer_watermark, fg_restore_info* info) {
+    if (!h) return FG_EINVAL;
+    if (n_images < 0 || (n_images > 0 && !images))
+        return h->fail(FG_EINVAL, "fg_restore_range: %d images", n_images);
+    if (location != FG_HOST && location != FG_DEVICE)
+        return h->fail(FG_EINVAL, "fg_restore_range: unknown location %d", location);
+    if (key_hash != FG_KEYHASH_BINARYROW_BIGINT && key_hash != FG_KEYHASH_JAVA_LONG && key_hash != FG_KEYHASH_DICT_ID)
+        return h->fail(FG_EINVAL, "fg_restore_range: unknown key hash %d", key_hash);
+    const fg_config& c = h->cfg;
+    if (!(0 <= c.key_group_start && c.key_group_start <= c.key_group_end && c.key_group_end < c.max_parallelism))
+        return h->fail(FG_EINVAL, "fg_restore_range: key-group range [%d, %d] is not within max parallelism %d",
+                       c.key_group_start, c.key_group_end, c.max_parallelism);
+    int64_t N = 0;
+    for (int32_t g = 0; g < n_images; g++) {
+        const fg_state_rows& im = images[g];
+        if (im.n < 0) return h->fail(FG_EINVAL, "fg_restore_range: image %d has %lld rows", g, (long long)im.n);
+        if (im.n == 0) continue;
+        if (!im.key || !im.slice_end || !im.cnt_star || !im.cnt_val || !im.sum)
+            return h->fail(FG_EINVAL, "fg_restore_range: image %d lacks a column", g);
+        if (h->mv && (!im.min || !im.max))
+            return h->fail(FG_EINVAL, "a multi-value operator's image needs the min and max columns");
+        N += im.n;
+        if (N >= ((int64_t)1 << 32))
+            return h->fail(FG_EINVAL, "fg_restore_range: the images hold 2^32 rows or more");
+    }
+    const bool was_empty = h->tables.empty();
+    h->cnt_bound = JMAX;
+    h->keys32 = false;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc0 = settle_pending(h)) return rc0;
+    int rc = flush(h);
+    if (rc) return rc;
+    fg_restore_info ri{};
+    ri.rows_in = N;
+    if (N > 0) {
+        rc = restore_range_rows(h, images, n_images, location, key_hash, N, &ri);
+        if (rc) return rc;
+    }
+    rc = restore_finish(h, timer_watermark, was_empty);
+    if (rc) return rc;
+    ri.state_regions = h->P;
+    if (info) *info = ri;
     return FG_OK;
 }
 

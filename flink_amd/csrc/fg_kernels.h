@@ -556,4 +556,68 @@ hipError_t launch_partition_by_owner(const int64_t* key, const int64_t* ts, cons
                                      size_t scratch_words, hipStream_t s);
 size_t partition_scratch_words(int64_t n, int32_t parallelism);
 
+// ---- rescale restore (fg_restore_range): the rows of several checkpoint images filtered by the
+// handle's key-group range and grouped by (slice, state region) into the SoA accumulator batch
+// (StagedBatch.is_acc) the merge consumes ----
+//   k_rr_dict     distinct slice ends of all rows into a small device table (wave-level dedup,
+//                 one 64-bit CAS per distinct value of a wave)
+//   k_rr_count    kept rows per (slice, top 13 bits of the key mix): the region sizing histogram
+//   k_rr_size     per slice and split b = 0 .. 13: the fullest region's rows
+//   k_rr_fold     the histogram at the chosen split, scanned into the (slice, region) offsets
+//   k_rr_scatter  kept rows into the batch, grouped by slice, then by region
+// k_rr_count and k_rr_scatter give each workgroup one row segment, which it walks once per
+// distinct slice end it holds (ascending) with an LDS counter per region: images list their
+// rows slice by slice, so a segment holds one or two. Global atomics are one per workgroup,
+// slice and non-empty region, never per row.
+constexpr int kRrMaxSlices = 4096;            // distinct slice ends per call
+constexpr int kRrDictSlots = 2 * kRrMaxSlices;
+constexpr int kRrHistBits = 13;               // = the engine's largest region split
+constexpr int kRrHist = 1 << kRrHistBits;
+constexpr int kRrThreads = 256;
+constexpr int kRrMaxGrid = 512;
+constexpr int64_t kRrSegment = 16384;         // rows per workgroup at least (below kRrMaxGrid workgroups)
+constexpr int kRrSizeCols = 16;               // k_rr_size: words per slice (entries 0 .. 13 used)
+struct RrImage {
+    const int64_t* key;
+    const int64_t* slice_end;
+    const int64_t* cnt_star;
+    const int64_t* cnt_val;
+    const int64_t* sum;
+    const int64_t* v1;         // multi-value operator: MIN / MAX (else null)
+    const int64_t* v2;
+    int64_t first;             // rows of the images before this one
+    int64_t n;
+};
+struct RrParams {
+    const RrImage* img;        // device array [n_images]
+    int32_t n_images;
+    int32_t grid;
+    int64_t n;                 // rows of all images (< 2^32)
+    int32_t key_hash, max_p;   // key_group_of's arguments
+    int32_t kg_lo, kg_hi;      // kept: kg_lo <= key group <= kg_hi
+    unsigned long long* dict;  // [kRrDictSlots] slice ends (kRrDictEmpty: free)
+    uint32_t* dict_n;          // [0] distinct values in dict, [1] some row holds kRrDictEmpty itself
+    const int64_t* slices;     // [n_slices] the distinct slice ends, ascending
+    int32_t n_slices;
+    int32_t region_bits;       // scatter: the regions of the batch
+    uint32_t* hist;            // [n_slices][kRrHist] kept rows (zeroed by the caller)
+    uint32_t* cursor;          // [n_slices << region_bits] next free position per (slice, region)
+    int64_t o_cap;             // rows of the batch (= the kept rows)
+    int64_t* o_key;            // the batch: key mix, COUNT(*), NULL count, sum (and MIN / MAX)
+    int64_t* o_cs;
+    int64_t* o_cn;
+    int64_t* o_sum;
+    int64_t* o_v1;
+    int64_t* o_v2;
+};
+constexpr unsigned long long kRrDictEmpty = ~0ull;   // (a memset pattern)
+int32_t rr_grid(int64_t n);
+hipError_t launch_rr_dict(const RrParams& p, hipStream_t s);
+hipError_t launch_rr_count(const RrParams& p, hipStream_t s);
+// out[s * kRrSizeCols + b]: the fullest of slice s's 2^b regions (b = 0: the slice's kept rows)
+hipError_t launch_rr_size(const uint32_t* hist, int32_t n_slices, uint32_t* out, hipStream_t s);
+// cnt[s << bits | r] = kept rows of slice s in region r at `bits`
+hipError_t launch_rr_fold(const uint32_t* hist, int32_t n_slices, int32_t bits, uint32_t* cnt, hipStream_t s);
+hipError_t launch_rr_scatter(const RrParams& p, hipStream_t s);
+
 }  // namespace fg

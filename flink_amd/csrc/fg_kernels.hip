@@ -14,6 +14,8 @@
 //                                      processors/SliceSharedWindowAggProcessor.java:64-118)
 //   k_export                           checkpoint image of the resident state
 //   k_key_groups / k_owner_*           KeyGroupRangeAssignment routing for the key-group exchange
+//   k_rr_*                             rescale restore: checkpoint images filtered by key-group range
+//                                      and grouped by (slice, region) for the merge
 //
 // All global traffic is streaming and coalesced; per-key read-modify-write happens in LDS
 // (ds_cmpst_rtn_b64 / ds_add_u64 / ds_add_f64), never as global atomics.
@@ -3066,6 +3068,248 @@ hipError_t launch_partition_by_owner(const int64_t* key, const int64_t* ts, cons
     fg_launch(k_owner_scatter, dim3(kOwnerGrid), dim3(kOwnerThreads), 0, s, key, ts, val, n, key_hash, max_p,
                        par, offs, out_key, out_ts, out_val);
     fg_launch(k_owner_counts, dim3(1), dim3(kMaxOwners), 0, s, offs, par, counts);
+    return hipGetLastError();
+}
+
+// ----------------------------------------------------------------------------------------
+// rescale restore (fg_kernels.h): key-group filter, slice dictionary, (slice, region) grouping
+// ----------------------------------------------------------------------------------------
+// the rows [beg, end) of the concatenated images, a workgroup's threads striding each image's part
+template <class F>
+__device__ __forceinline__ void rr_rows(const RrParams& p, int64_t beg, int64_t end, F f) {
+    for (int g = 0; g < p.n_images; g++) {
+        const RrImage d = p.img[g];
+        const int64_t lo = (beg > d.first ? beg : d.first) - d.first;
+        const int64_t hi = (end < d.first + d.n ? end : d.first + d.n) - d.first;
+        for (int64_t i = lo + threadIdx.x; i < hi; i += kRrThreads) f(d, i);
+    }
+}
+__device__ __forceinline__ bool rr_keep(const RrParams& p, int64_t key) {
+    const int32_t kg = key_group_of(key, p.key_hash, p.max_p);
+    return kg >= p.kg_lo && kg <= p.kg_hi;
+}
+// slice ends in unsigned order
+__device__ __forceinline__ uint64_t rr_ord(int64_t se) { return (uint64_t)se ^ (1ull << 63); }
+__device__ __forceinline__ uint32_t rr_region(int64_t key, int bits) {
+    return bits == 0 ? 0u : (uint32_t)(fmix64((uint64_t)key) >> (64 - bits));
+}
+
+__device__ __forceinline__ void rr_dict_insert(const RrParams& p, int64_t v) {
+    if ((unsigned long long)v == kRrDictEmpty) {
+        p.dict_n[1] = 1u;
+        return;
+    }
+    // past the limit the call fails whatever else the rows hold: the table never fills up
+    if (__hip_atomic_load(&p.dict_n[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > (uint32_t)kRrMaxSlices) return;
+    uint32_t s = (uint32_t)fmix64((uint64_t)v) & (uint32_t)(kRrDictSlots - 1);
+    for (int probe = 0; probe < kRrDictSlots; probe++) {
+        const unsigned long long old = atomicCAS(&p.dict[s], kRrDictEmpty, (unsigned long long)v);
+        if (old == kRrDictEmpty) {
+            atomicAdd(&p.dict_n[0], 1u);
+            return;
+        }
+        if (old == (unsigned long long)v) return;
+        s = (s + 1) & (uint32_t)(kRrDictSlots - 1);
+    }
+}
+
+// Distinct slice ends: the lanes of a wave mostly share one, so the wave takes its first
+// pending lane's value, retires every lane that holds it and lets that lane alone insert --
+// and not even that while the value is the one the wave inserted last.
+__global__ __launch_bounds__(kRrThreads) void k_rr_dict(RrParams p) {
+    int64_t beg, end;
+    seg_bounds(p.n, p.grid, blockIdx.x, &beg, &end);
+    const int lane = threadIdx.x & 63;
+    long long last = 0;
+    bool have_last = false;
+    for (int g = 0; g < p.n_images; g++) {
+        const RrImage d = p.img[g];
+        const int64_t lo = (beg > d.first ? beg : d.first) - d.first;
+        const int64_t hi = (end < d.first + d.n ? end : d.first + d.n) - d.first;
+        for (int64_t ib = lo; ib < hi; ib += kRrThreads) {   // workgroup-uniform trip count
+            const int64_t i = ib + threadIdx.x;
+            const bool valid = i < hi;
+            const long long se = valid ? (long long)gbl(d.slice_end)[i] : 0;
+            bool todo = valid;
+            for (;;) {
+                const unsigned long long m = __ballot(todo);
+                if (m == 0) break;
+                const int leader = __ffsll((long long)m) - 1;
+                const long long v = __shfl(se, leader);
+                if (todo && se == v) todo = false;
+                if (!have_last || v != last) {
+                    if (lane == leader) rr_dict_insert(p, (int64_t)v);
+                    last = v;
+                    have_last = true;
+                }
+            }
+        }
+    }
+}
+
+// One workgroup per row segment, one pass over the segment per distinct slice end of its kept
+// rows, ascending: a pass counts the rows of the current slice per region in LDS and finds the
+// next slice end. Count: the LDS counters (13 region bits) are added to the slice's histogram.
+// Scatter: each non-empty region reserves its rows' positions from the (slice, region) cursor
+// (one global atomic), and a second walk moves the rows there.
+template <bool SCATTER>
+__global__ __launch_bounds__(kRrThreads) void k_rr_pass(RrParams p) {
+    __shared__ uint32_t s_h[kRrHist];
+    __shared__ unsigned long long s_min[kRrThreads / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int bits = SCATTER ? p.region_bits : kRrHistBits;
+    const int NB = 1 << bits;
+    for (int r = tid; r < NB; r += kRrThreads) s_h[r] = 0;
+    __syncthreads();
+    int64_t beg, end;
+    seg_bounds(p.n, p.grid, blockIdx.x, &beg, &end);
+    bool first = true;       // the first pass only finds the smallest slice end
+    uint64_t cur = 0;        // the pass's slice end (rr_ord), workgroup-uniform
+    int sidx = 0;            // its index in p.slices
+    for (;;) {
+        unsigned long long nx = ~0ull;
+        bool has = false;
+        rr_rows(p, beg, end, [&](const RrImage& d, int64_t i) {
+            const int64_t key = gbl(d.key)[i];
+            if (!rr_keep(p, key)) return;
+            const uint64_t u = rr_ord(gbl(d.slice_end)[i]);
+            if (!first && u == cur) {
+                atomicAdd(&s_h[rr_region(key, bits)], 1u);
+            } else if (first || u > cur) {
+                nx = u < nx ? u : nx;
+                has = true;
+            }
+        });
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long t = __shfl_xor(nx, o);
+            nx = t < nx ? t : nx;
+        }
+        if (lane == 0) s_min[wave] = nx;
+        const int any = __syncthreads_or(has ? 1 : 0);
+        if (!first) {
+            if constexpr (SCATTER) {
+                uint32_t* cursor = p.cursor + ((int64_t)sidx << bits);
+                for (int r = tid; r < NB; r += kRrThreads) {
+                    const uint32_t c = s_h[r];
+                    if (c) s_h[r] = atomicAdd(&cursor[r], c);
+                }
+                __syncthreads();
+                rr_rows(p, beg, end, [&](const RrImage& d, int64_t i) {
+                    const int64_t key = gbl(d.key)[i];
+                    if (!rr_keep(p, key) || rr_ord(gbl(d.slice_end)[i]) != cur) return;
+                    const int64_t pos = (int64_t)atomicAdd(&s_h[rr_region(key, bits)], 1u);
+                    if (pos >= p.o_cap) return;   // (the images changed between the passes)
+                    const int64_t cs = gbl(d.cnt_star)[i];
+                    p.o_key[pos] = mix_of(key);
+                    p.o_cs[pos] = cs;
+                    p.o_cn[pos] = jsub(cs, gbl(d.cnt_val)[i]);
+                    p.o_sum[pos] = gbl(d.sum)[i];
+                    if (p.o_v1 != nullptr) {
+                        p.o_v1[pos] = gbl(d.v1)[i];
+                        p.o_v2[pos] = gbl(d.v2)[i];
+                    }
+                });
+                __syncthreads();
+                for (int r = tid; r < NB; r += kRrThreads) s_h[r] = 0;
+            } else {
+                uint32_t* hist = p.hist + (int64_t)sidx * kRrHist;
+                for (int r = tid; r < NB; r += kRrThreads) {
+                    const uint32_t c = s_h[r];
+                    if (c) {
+                        atomicAdd(&hist[r], c);
+                        s_h[r] = 0;
+                    }
+                }
+            }
+        }
+        if (!any) break;
+        unsigned long long m = s_min[0];
+        for (int w = 1; w < kRrThreads / 64; w++) m = s_min[w] < m ? s_min[w] : m;
+        cur = m;
+        first = false;
+        const int64_t se = (int64_t)(cur ^ (1ull << 63));
+        int lo = 0, hi = p.n_slices - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (gbl(p.slices)[mid] < se) lo = mid + 1;
+            else hi = mid;
+        }
+        sidx = lo;
+        __syncthreads();
+    }
+}
+
+// per slice: the fullest region at every split 2^b, b = 13 .. 0, by pairwise sums of the histogram
+__global__ __launch_bounds__(kRrThreads) void k_rr_size(const uint32_t* hist, uint32_t* out) {
+    __shared__ uint32_t s_a[kRrHist];
+    __shared__ uint32_t s_b[kRrHist / 2];
+    __shared__ uint32_t s_mx[kRrHistBits + 1];
+    const int s = blockIdx.x, tid = threadIdx.x;
+    for (int i = tid; i < kRrHist; i += kRrThreads) s_a[i] = gbl(hist)[(int64_t)s * kRrHist + i];
+    if (tid <= kRrHistBits) s_mx[tid] = 0;
+    __syncthreads();
+    uint32_t* src = s_a;
+    uint32_t* dst = s_b;
+    for (int b = kRrHistBits; b >= 0; b--) {
+        const int L = 1 << b;
+        uint32_t m = 0;
+        for (int i = tid; i < L; i += kRrThreads) m = src[i] > m ? src[i] : m;
+        if (m) atomicMax(&s_mx[b], m);
+        for (int i = tid; i < L / 2; i += kRrThreads) dst[i] = src[2 * i] + src[2 * i + 1];
+        __syncthreads();
+        uint32_t* t = src;
+        src = dst;
+        dst = t;
+    }
+    if (tid <= kRrHistBits) out[(int64_t)s * kRrSizeCols + tid] = s_mx[tid];
+}
+
+__global__ void k_rr_fold(const uint32_t* hist, int64_t n, int32_t bits, uint32_t* cnt) {
+    const int per = kRrHist >> bits;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        uint32_t sum = 0;
+        for (int c = 0; c < per; c++) sum += gbl(hist)[i * per + c];
+        cnt[i] = sum;
+    }
+}
+
+int32_t rr_grid(int64_t n) {
+    const int64_t g = (n + kRrSegment - 1) / kRrSegment;
+    return (int32_t)std::min<int64_t>(std::max<int64_t>(g, 1), kRrMaxGrid);
+}
+static bool rr_params_ok(const RrParams& p) {
+    return p.img != nullptr && p.n_images >= 1 && p.grid >= 1 && p.grid <= kRrMaxGrid && p.n >= 1 &&
+           p.n < ((int64_t)1 << 32);
+}
+hipError_t launch_rr_dict(const RrParams& p, hipStream_t s) {
+    if (!rr_params_ok(p) || !p.dict || !p.dict_n) return hipErrorInvalidValue;
+    fg_launch(k_rr_dict, dim3(p.grid), dim3(kRrThreads), 0, s, p);
+    return hipGetLastError();
+}
+hipError_t launch_rr_count(const RrParams& p, hipStream_t s) {
+    if (!rr_params_ok(p) || !p.slices || p.n_slices < 1 || p.n_slices > kRrMaxSlices || !p.hist)
+        return hipErrorInvalidValue;
+    fg_launch(k_rr_pass<false>, dim3(p.grid), dim3(kRrThreads), 0, s, p);
+    return hipGetLastError();
+}
+hipError_t launch_rr_size(const uint32_t* hist, int32_t n_slices, uint32_t* out, hipStream_t s) {
+    if (n_slices < 1 || n_slices > kRrMaxSlices) return hipErrorInvalidValue;
+    fg_launch(k_rr_size, dim3(n_slices), dim3(kRrThreads), 0, s, hist, out);
+    return hipGetLastError();
+}
+hipError_t launch_rr_fold(const uint32_t* hist, int32_t n_slices, int32_t bits, uint32_t* cnt, hipStream_t s) {
+    if (n_slices < 1 || n_slices > kRrMaxSlices || bits < 0 || bits > kRrHistBits) return hipErrorInvalidValue;
+    const int64_t n = (int64_t)n_slices << bits;
+    const int64_t blocks = std::min<int64_t>((n + 255) / 256, 4096);
+    fg_launch(k_rr_fold, dim3((unsigned)blocks), dim3(256), 0, s, hist, n, bits, cnt);
+    return hipGetLastError();
+}
+hipError_t launch_rr_scatter(const RrParams& p, hipStream_t s) {
+    if (!rr_params_ok(p) || !p.slices || p.n_slices < 1 || p.n_slices > kRrMaxSlices || p.region_bits < 0 ||
+        p.region_bits > kRrHistBits || !p.cursor || !p.o_key || !p.o_cs || !p.o_cn || !p.o_sum ||
+        (p.o_v1 != nullptr) != (p.o_v2 != nullptr))
+        return hipErrorInvalidValue;
+    fg_launch(k_rr_pass<true>, dim3(p.grid), dim3(kRrThreads), 0, s, p);
     return hipGetLastError();
 }
 

@@ -361,3 +361,12 @@ def union_image_for(images, key_group_range, max_parallelism=128, key_groups=Non
     keep = (kg >= lo) & (kg <= hi)
     twm = min(w for _, w in images)
     return {c: v[keep] for c, v in cat.items()}, twm
+
+
+def restore_union(glob, images, key_hash=None):
+    """union_image_for followed by restore_state, with the key-group filter on the GPU: the global
+    operator `glob` (a WindowAggOperator opened with this subtask's key_group_range) takes the
+    (image, timer watermark) pairs of every subtask's global image as they are and keeps the
+    entries of its own key groups (fg_restore_range). Returns the restore's info dict."""
+    from . import _lib as L
+    return glob.restore_state_range(images, None, L.KEYHASH_BINARYROW_BIGINT if key_hash is None else key_hash)

@@ -514,6 +514,55 @@ class WindowAggOperator:
             setattr(s, k, cols[k].ctypes.data)
         L.check(self._lib.fg_restore(self._h, C.byref(s), int(timer_watermark)), self._h)
 
+    def restore_state_range(self, images, timer_watermark=None, key_hash=L.KEYHASH_BINARYROW_BIGINT) -> dict:
+        """Rescale restore (fg_restore_range): restore_state of the concatenation of `images`,
+        restricted on the GPU to the rows whose key group lies in this operator's
+        key_group_range -- what a subtask does after a restart at another parallelism with the
+        images of every old subtask.
+
+        images: (image dict, timer watermark) pairs or plain image dicts; the columns of one call
+        are all numpy arrays (host) or all torch CUDA int64 tensors (read in place).
+        timer_watermark=None takes the minimum of the pairs' watermarks. Returns the
+        fg_restore_info fields: rows_in, rows_kept, slices, state_regions."""
+        imgs, wms = [], []
+        for it in images:
+            if isinstance(it, (tuple, list)):
+                imgs.append(it[0])
+                wms.append(int(it[1]))
+            else:
+                imgs.append(it)
+        if timer_watermark is None:
+            if len(wms) != len(imgs) or not wms:
+                raise ValueError("restore_state_range: timer_watermark=None needs (image, watermark) pairs")
+            timer_watermark = min(wms)
+        arr = (L.FgStateRows * max(len(imgs), 1))()
+        keep, on_device = [], set()
+        for s, image in zip(arr, imgs):
+            s.n = len(image["key"])
+            for k in ("key", "slice_end", "cnt_star", "cnt_val", "sum", "min", "max"):
+                x = image.get(k)
+                if x is None:
+                    continue
+                if not (hasattr(x, "is_cuda") and x.is_cuda):
+                    x = np.ascontiguousarray(x, dtype=np.int64)
+                elif str(x.dtype) != "torch.int64":
+                    raise TypeError(f"restore_state_range: device column {k} must be int64")
+                if len(x) != s.n:
+                    raise ValueError(f"restore_state_range: column {k} has {len(x)} rows, key has {s.n}")
+                ptr, dev, x = _dev_ptr(x)
+                keep.append(x)
+                on_device.add(bool(dev))
+                setattr(s, k, ptr if dev else x.ctypes.data)
+        if len(on_device) > 1:
+            raise ValueError("restore_state_range: the columns of one call share one location")
+        dev = on_device == {True}
+        if dev:
+            self._after_producers(keep)
+        info = L.FgRestoreInfo()
+        L.check(self._lib.fg_restore_range(self._h, arr, len(imgs), L.DEVICE if dev else L.HOST, int(key_hash),
+                                           int(timer_watermark), C.byref(info)), self._h)
+        return {k: int(getattr(info, k)) for k, _ in info._fields_}
+
     # -- metrics ------------------------------------------------------------------------------------
     @property
     def num_late_records_dropped(self) -> int:

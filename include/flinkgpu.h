@@ -24,6 +24,9 @@
  *   StreamOperatorStateHandler.snapshotState (window-aggs state + timers)   fg_snapshot_state
  *     SJ/api/operators/StreamOperatorStateHandler.java:185-241
  *   AbstractStreamOperator.initializeState (keyed state restore)         fg_restore
+ *   AbstractStreamOperator.initializeState after a rescale: KeyGroupRangeAssignment /
+ *     StateAssignmentOperation (each new subtask takes its key-group range out of every
+ *     old subtask's state)                                                fg_restore_range
  *   SlicingWindowOperator.getNumLateRecordsDropped :300-303            fg_late_dropped
  *   two-phase: LocalAggCombiner.combine (local operator output)        fg_config.flags |= FG_FLAG_LOCAL_PARTIALS
  *     GlobalAggCombiner.combine  .../combines/GlobalAggCombiner.java:77-110  fg_add_partials
@@ -362,6 +365,39 @@ int  fg_snapshot_slices(fg_handle* h, fg_image_slices* out);
  * rows. */
 int  fg_selftest(int32_t device_id, char* msg, int32_t cap);
 int  fg_restore(fg_handle* h, const fg_state_rows* in, int64_t timer_watermark);
+/* Rescale restore (ABI 16, added): fg_restore of the concatenation of images[0 .. n_images),
+ * restricted to the rows whose key group lies in the handle's range,
+ *   fg_config.key_group_start <= key_group(key, key_hash, fg_config.max_parallelism) <= key_group_end
+ * (KeyGroupRangeAssignment; a restart at another parallelism hands every new subtask the images of
+ * all old subtasks). The state after the call is what fg_restore leaves for that filtered image.
+ * The filter, the grouping by slice and state region and the scatter run as kernels on the
+ * handle's stream; the host never reads a row.
+ *  - timer_watermark: the minimum over the images' timer watermarks.
+ *  - location FG_HOST: pageable or pinned columns, copied up on the handle's stream and read when the
+ *    call returns. FG_DEVICE: device columns read in place on the handle's stream (the ordering rule
+ *    of fg_location applies); they must not change during the call.
+ *  - Rows may come in any order and a slice may occur in several images; duplicate (key, slice)
+ *    rows merge as fg_restore merges them. With three or more DOUBLE duplicates of one (key, slice)
+ *    the summation order is unspecified. Rows listed slice by slice (as fg_snapshot_state writes
+ *    them) are the fast case: the grouping walks a run of rows once per distinct slice end in it.
+ *  - At most 4096 distinct slice ends among the rows of all images (foreign rows included) and fewer
+ *    than 2^32 rows per call, else FG_EINVAL.
+ *  - FG_EINVAL, before any device work: n_images < 0; an image with n > 0 and a NULL key, slice_end,
+ *    cnt_star, cnt_val or sum; a NULL min or max for an operator with several value accumulators; an
+ *    unknown key_hash or location; a handle whose range is not 0 <= start <= end < max_parallelism
+ *    (fg_open does not check the range). The handle stays usable.
+ *  - No image (n_images == 0) or only foreign rows: a valid restore of an empty image.
+ *  - Device memory during the call, freed on return: 8 B x columns (5, or 7 with min / max) per input
+ *    row for FG_HOST images (they are uploaded whole), 8 B x (4, or 6) per kept row for the grouped
+ *    batch, and 32 KiB + 12 B x state regions per distinct slice end for the histograms. */
+typedef struct fg_restore_info {
+    int64_t rows_in;        /* rows of all images */
+    int64_t rows_kept;      /* rows whose key group lies in the handle's range */
+    int64_t slices;         /* distinct slice ends among the kept rows */
+    int64_t state_regions;  /* regions per slice table after the restore (fg_stats.state_regions) */
+} fg_restore_info;
+int  fg_restore_range(fg_handle* h, const fg_state_rows* images, int32_t n_images, int32_t location,
+                      int32_t key_hash, int64_t timer_watermark, fg_restore_info* info /* may be NULL */);
 int  fg_late_dropped(fg_handle* h, int64_t* out);
 int  fg_get_stats(fg_handle* h, fg_stats* out);
 int  fg_synchronize(fg_handle* h);

@@ -129,6 +129,25 @@ public final class FlinkGpu {
             ByteBuffer max,
             long timerWatermark);
 
+    /**
+     * fg_restore_range over one host image: restore of the rows whose key group (keyHash, the
+     * handle's max parallelism) lies in the handle's key-group range, filtered and grouped on the
+     * GPU; returns the rows kept. What a subtask calls with every old subtask's image after a
+     * restart at another parallelism.
+     */
+    public static native long restoreRange(
+            long h,
+            int n,
+            ByteBuffer key,
+            ByteBuffer sliceEnd,
+            ByteBuffer cntStar,
+            ByteBuffer cntVal,
+            ByteBuffer sum,
+            ByteBuffer min,
+            ByteBuffer max,
+            int keyHash,
+            long timerWatermark);
+
     /** fg_late_dropped (numLateRecordsDropped). */
     public static native long lateDropped(long h);
 

@@ -532,38 +532,46 @@ public final class GpuTwoPhaseWindowAggOperator extends TableStreamOperator<RowD
         return out;
     }
 
-    /** initializeState: every subtask's chunks, the entries of this subtask's key groups kept */
+    /**
+     * initializeState: every subtask's chunks decoded straight into seven direct column buffers;
+     * the global handle, opened with this subtask's key-group range, keeps the entries of its own
+     * key groups on the GPU (fg_restore_range). A subtask that owns every key group keeps them all.
+     */
     private void restoreGlobal(KeyGroupRange range) {
         if (restoredImage == null || restoredImage.isEmpty()) {
             return;
         }
         long timerWm = Long.MAX_VALUE;
-        List<long[]> rows = new ArrayList<>();
+        long total = 0;
         for (byte[] chunk : restoredImage) {
             ByteBuffer b = ByteBuffer.wrap(chunk).order(ByteOrder.LITTLE_ENDIAN);
-            long n = b.getLong();
+            total += b.getLong();
             timerWm = Math.min(timerWm, b.getLong());
-            for (long i = 0; i < n; i++) {
-                long[] row = new long[7];
-                for (int c = 0; c < 7; c++) {
-                    row[c] = b.getLong();
-                }
-                RowData key = keys.rows(GpuKeyRows.direct(8).putLong(0, row[0]), 1)[0];
-                if (range.contains(KeyGroupRangeAssignment.assignToKeyGroup(key, maxP))) {
-                    rows.add(row);
-                }
-            }
         }
-        int n = rows.size();
+        int n = Math.toIntExact(total);
         ByteBuffer[] c = new ByteBuffer[7];
         for (int j = 0; j < 7; j++) {
             c[j] = GpuKeyRows.direct(8L * Math.max(n, 1));
-            for (int i = 0; i < n; i++) {
-                c[j].putLong(8 * i, rows.get(i)[j]);
+        }
+        int at = 0;
+        for (byte[] chunk : restoredImage) {
+            ByteBuffer b = ByteBuffer.wrap(chunk).order(ByteOrder.LITTLE_ENDIAN);
+            long rows = b.getLong();
+            b.getLong();
+            for (long i = 0; i < rows; i++, at++) {
+                for (int j = 0; j < 7; j++) {
+                    c[j].putLong(8 * at, b.getLong());
+                }
             }
         }
         boolean mv = accRows.multiValue();
-        FlinkGpu.restore(global, n, c[0], c[1], c[2], c[3], c[4], mv ? c[5] : null, mv ? c[6] : null, timerWm);
+        ByteBuffer min = mv ? c[5] : null, max = mv ? c[6] : null;
+        if (range.getNumberOfKeyGroups() == maxP) {
+            FlinkGpu.restore(global, n, c[0], c[1], c[2], c[3], c[4], min, max, timerWm);
+        } else {
+            FlinkGpu.restoreRange(
+                    global, n, c[0], c[1], c[2], c[3], c[4], min, max, FlinkGpu.KEYHASH_BINARYROW_BIGINT, timerWm);
+        }
         restoredImage = null;
     }
 }

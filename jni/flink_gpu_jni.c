@@ -358,6 +358,32 @@ JNIEXPORT void JNICALL FN(restore)(JNIEnv* env, jclass cls, jlong hp, jint n, jo
     check(env, h, fg_restore(h, &s, timerWm));
 }
 
+/* long restoreRange(long h, int n, ByteBuffer key, ByteBuffer sliceEnd, ByteBuffer cntStar, ByteBuffer cntVal,
+ *                   ByteBuffer sum, ByteBuffer min, ByteBuffer max, int keyHash, long timerWatermark):
+ * restore of the rows whose key group lies in the handle's range (fg_restore_range over one host
+ * image, filtered on the GPU); returns the rows kept */
+JNIEXPORT jlong JNICALL FN(restoreRange)(JNIEnv* env, jclass cls, jlong hp, jint n, jobject key, jobject sliceEnd,
+                                         jobject cntStar, jobject cntVal, jobject sum, jobject min, jobject max,
+                                         jint keyHash, jlong timerWm) {
+    (void)cls;
+    fg_handle* h = (fg_handle*)(intptr_t)hp;
+    fg_state_rows s;
+    fg_restore_info info;
+    memset(&s, 0, sizeof s);
+    memset(&info, 0, sizeof info);
+    s.n = n;
+    s.key = (const int64_t*)addr(env, key);
+    s.slice_end = (const int64_t*)addr(env, sliceEnd);
+    s.cnt_star = (const int64_t*)addr(env, cntStar);
+    s.cnt_val = (const int64_t*)addr(env, cntVal);
+    s.sum = (const int64_t*)addr(env, sum);
+    s.min = (const int64_t*)addr(env, min);
+    s.max = (const int64_t*)addr(env, max);
+    if ((*env)->ExceptionCheck(env)) return 0;
+    check(env, h, fg_restore_range(h, &s, 1, FG_HOST, keyHash, timerWm, &info));
+    return info.rows_kept;
+}
+
 /* long lateDropped(long h) */
 JNIEXPORT jlong JNICALL FN(lateDropped)(JNIEnv* env, jclass cls, jlong hp) {
     (void)cls;
