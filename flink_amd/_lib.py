@@ -95,6 +95,10 @@ class FgImageSlices(C.Structure):
                 ("changed", C.c_void_p)]
 
 
+class FgImageKeyGroups(C.Structure):
+    _fields_ = [("n_slices", C.c_int64), ("max_parallelism", C.c_int32), ("first_row", C.c_void_p)]
+
+
 class FgStats(C.Structure):
     _fields_ = [(n, C.c_int64) for n in (
         "records_in", "records_staged", "late_dropped", "rows_fired", "flushes", "live_slices",
@@ -123,6 +127,7 @@ EXPORTS = (
     "fg_advance_progress_async_n",
     "fg_collect_fired", "fg_collect_fired_to", "fg_flush", "fg_flush_partials", "fg_snapshot_state",
     "fg_snapshot_state_async", "fg_snapshot_state_wait", "fg_snapshot_slices", "fg_selftest", "fg_restore", "fg_restore_range", "fg_late_dropped", "fg_get_stats", "fg_synchronize", "fg_reset", "fg_kernel_stats", "fg_set_kernel_timing",
+    "fg_set_snapshot_grouping", "fg_snapshot_key_groups",
     "fg_stream",
     "fg_last_error", "fg_close", "fg_key_groups", "fg_partition_by_owner", "fg_partition_columns_by_owner",
     "fg_abi_version", "fg_key_dict_open", "fg_key_dict_intern", "fg_key_dict_intern_async",
@@ -236,6 +241,8 @@ def load():
     L.fg_comm_round_exchange.argtypes = [P, C.POINTER(FgRound)]
     L.fg_comm_round_end.argtypes = [P, P]
     L.fg_snapshot_slices.argtypes = [P, C.POINTER(FgImageSlices)]
+    L.fg_set_snapshot_grouping.argtypes = [P, C.c_int32]
+    L.fg_snapshot_key_groups.argtypes = [P, C.POINTER(FgImageKeyGroups)]
     L.fg_selftest.argtypes = [C.c_int32, C.c_char_p, C.c_int32]
     L.fg_selftest.restype = C.c_int
     L.fg_comm_bytes_sent.argtypes = [P]
@@ -256,7 +263,7 @@ def load():
         getattr(L, fn).restype = C.c_int
     for fn in ("fg_open", "fg_add_batch", "fg_add_rows", "fg_add_partials", "fg_advance_progress",
                "fg_advance_progress_async", "fg_advance_progress_async_n", "fg_collect_fired", "fg_collect_fired_to", "fg_flush", "fg_flush_partials",
-               "fg_snapshot_state", "fg_snapshot_state_async", "fg_snapshot_state_wait", "fg_snapshot_slices", "fg_restore", "fg_restore_range", "fg_late_dropped", "fg_get_stats", "fg_synchronize", "fg_reset", "fg_kernel_stats", "fg_key_groups",
+               "fg_snapshot_state", "fg_snapshot_state_async", "fg_snapshot_state_wait", "fg_snapshot_slices", "fg_set_snapshot_grouping", "fg_snapshot_key_groups", "fg_restore", "fg_restore_range", "fg_late_dropped", "fg_get_stats", "fg_synchronize", "fg_reset", "fg_kernel_stats", "fg_key_groups",
                "fg_partition_by_owner", "fg_partition_columns_by_owner"):
         getattr(L, fn).restype = C.c_int
     _lib = L

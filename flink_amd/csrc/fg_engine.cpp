@@ -175,12 +175,12 @@ constexpr int64_t kHeavyChunk = 1 << 16;
 
 enum KClass { K_COUNT = 0, K_SCAN, K_SCATTER, K_PART1, K_PART2, K_FLUSH, K_FLUSH_FIRE, K_FIRE, K_EXPORT, K_RESTORE,
               K_HEAVY, K_TILE1, K_TILE_FIRE, K_TILE_MAT, K_TILE_FLUSH, K_TILE_SPLIT, K_RR_FILTER, K_RR_SCATTER,
-              K_NCLASS };
+              K_EXPORT_GROUP, K_NCLASS };
 const char* const kClassName[K_NCLASS] = {"ingest_count", "ingest_scan",      "ingest_scatter", "ingest_part1",
                                            "ingest_part2", "merge_flush",      "merge_flush_fire", "merge_fire",
                                            "export",       "restore",          "merge_heavy",      "tile_part1",
                                            "tile_fire",    "tile_materialize", "tile_flush",       "tile_split_fire",
-                                           "restore_filter", "restore_scatter"};
+                                           "restore_filter", "restore_scatter", "export_group"};
 struct KStat {
     int64_t launches = 0;
     double ms = 0;
@@ -315,6 +315,15 @@ struct fg_handle {
     std::vector<int64_t> img_se, img_first, img_rows;
     std::vector<uint8_t> img_changed;
     bool img_ready = false;   // an image was returned since the last snapshot call
+    // key-grouped images (fg_set_snapshot_grouping): the key hash (< 0: off), the second column set
+    // the export's rows are scattered into (the D2H source), the (slice, key group) counters and
+    // offsets, and the last image's index (fg_snapshot_key_groups)
+    int32_t snap_group = -1;
+    bool snap_grouped = false;   // the pending / last image is grouped
+    int64_t snap_bins = 0;       // its slices x max_parallelism
+    DevBuf g_key, g_cs, g_cv, g_sum, g_v1, g_v2, kg_first, kg_cnt, kg_off, kg_tmp;
+    HostBuf hs_kg_first, hs_kg_off;
+    std::vector<int64_t> img_kg_first;
     DevBuf hb_key[2], hb_ts[2], hb_val[2], hb_null[2];
     DevBuf hb_narrow[2];   // FG_HOST narrow columns (fg_batch.format) before widening
     hipEvent_t ev_copied[2] = {nullptr, nullptr}, ev_free[2] = {nullptr, nullptr};
@@ -4179,6 +4188,64 @@ int fg_advance_progress(fg_handle* h, int64_t wm, int32_t out_location, fg_rows*
     return FG_OK;
 }
 
+// fg_set_snapshot_grouping: the exported image (s_*, `total` rows in the slices of img_first)
+// reordered by key group inside every slice into the second column set (g_*) on the handle's
+// stream; kg_off: the row offset of every (slice, key group). The slice_end column keeps its
+// place (a row stays in its slice), and an aliased cnt_val column is not moved.
+static int snapshot_group(fg_handle* h, int64_t total) {
+    const int64_t S = (int64_t)h->img_se.size(), maxp = h->cfg.max_parallelism;
+    if (S * maxp > kKgMaxBins || total >= ((int64_t)1 << 32))
+        return h->fail(FG_EINVAL, "grouped snapshot: more than 2^30 (slice, key group) pairs or 2^32 rows");
+    h->snap_bins = S * maxp;
+    if (total == 0) return FG_OK;
+    const int64_t bins = h->snap_bins;
+    HIPCHK(h, h->hs_kg_first.ensure(8 * (size_t)(S + 1)));
+    for (int64_t s = 0; s < S; s++) h->hs_kg_first.as<int64_t>()[s] = h->img_first[(size_t)s];
+    h->hs_kg_first.as<int64_t>()[S] = total;
+    HIPCHK(h, h->kg_first.ensure(8 * (size_t)(S + 1)));
+    HIPCHK(h, h->kg_cnt.ensure(4 * (size_t)bins));
+    HIPCHK(h, h->kg_off.ensure(4 * (size_t)(bins + 1)));
+    HIPCHK(h, h->kg_tmp.ensure(4 * scan_tmp_words(bins)));
+    HIPCHK(h, h->hs_kg_off.ensure(4 * (size_t)(bins + 1)));
+    bool any_null = false;
+    for (auto& kv : h->tables) any_null = any_null || kv.second->has_null;
+    const size_t b8 = 8 * (size_t)total;
+    KgParams p{};
+    p.key = h->s_key.as<int64_t>();
+    p.n = total;
+    p.slice_first = h->kg_first.as<int64_t>();
+    p.n_slices = (int32_t)S;
+    p.grid = rr_grid(total);
+    p.key_hash = h->snap_group;
+    p.max_p = (int32_t)maxp;
+    p.cnt = h->kg_cnt.as<uint32_t>();
+    p.off = h->kg_off.as<uint32_t>();
+    auto col = [&](DevBuf& src, DevBuf& dst) -> hipError_t {
+        hipError_t e = dst.ensure(b8);
+        p.src[p.n_cols] = src.as<int64_t>();
+        p.dst[p.n_cols] = dst.as<int64_t>();
+        p.n_cols++;
+        return e;
+    };
+    HIPCHK(h, col(h->s_key, h->g_key));
+    HIPCHK(h, col(h->s_cs, h->g_cs));
+    if (any_null) HIPCHK(h, col(h->s_cv, h->g_cv));
+    HIPCHK(h, col(h->s_sum, h->g_sum));
+    if (h->mv) {
+        HIPCHK(h, col(h->s_v1, h->g_v1));
+        HIPCHK(h, col(h->s_v2, h->g_v2));
+    }
+    HIPCHK(h, hipMemcpyAsync(h->kg_first.p, h->hs_kg_first.p, 8 * (size_t)(S + 1), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(h->kg_cnt.p, 0, 4 * (size_t)bins, h->stream));
+    {
+        KTimer kt(h, K_EXPORT_GROUP, total);
+        HIPCHK(h, launch_kg_count(p, h->stream));
+        HIPCHK(h, launch_scan_u32(p.cnt, h->kg_off.as<uint32_t>(), bins, h->kg_tmp.as<uint32_t>(), h->stream));
+        HIPCHK(h, launch_kg_scatter(p, h->stream));
+    }
+    return FG_OK;
+}
+
 // snapshotState's synchronous part: the staged records flushed, every resident slice exported
 // into the device image columns (s_*, in stream order: the image is the state as of this call)
 // and their copy into the pinned host image (hs_*) queued on the snapshot stream
@@ -4271,6 +4338,19 @@ static int snapshot_begin(fg_handle* h) {
         HIPCHK(h, h->hs_v1.ensure(b8));
         HIPCHK(h, h->hs_v2.ensure(b8));
     }
+    h->snap_grouped = h->snap_group >= 0;
+    const int64_t *d_key = h->s_key.as<int64_t>(), *d_cs = h->s_cs.as<int64_t>(), *d_cv = h->s_cv.as<int64_t>(),
+                  *d_sum = h->s_sum.as<int64_t>(), *d_v1 = h->s_v1.as<int64_t>(), *d_v2 = h->s_v2.as<int64_t>();
+    if (h->snap_grouped) {
+        if (int rcg = snapshot_group(h, total)) {
+            h->snap_grouped = false;
+            return rcg;
+        }
+        if (total > 0) {
+            d_key = h->g_key.as<int64_t>(), d_cs = h->g_cs.as<int64_t>(), d_cv = h->g_cv.as<int64_t>();
+            d_sum = h->g_sum.as<int64_t>(), d_v1 = h->g_v1.as<int64_t>(), d_v2 = h->g_v2.as<int64_t>();
+        }
+    }
     if (total > 0) {
         if (!h->snap_stream) {
             // (the runtime copies device -> host with blit kernels that share the CUs with a
@@ -4284,19 +4364,21 @@ static int snapshot_begin(fg_handle* h) {
         hipStream_t cs = h->snap_stream;
         const hipMemcpyKind kd = hipMemcpyDeviceToHost;
         if (h->mv) {
-            HIPCHK(h, hipMemcpyAsync(h->hs_v1.p, h->s_v1.p, 8 * total, kd, cs));
-            HIPCHK(h, hipMemcpyAsync(h->hs_v2.p, h->s_v2.p, 8 * total, kd, cs));
+            HIPCHK(h, hipMemcpyAsync(h->hs_v1.p, d_v1, 8 * total, kd, cs));
+            HIPCHK(h, hipMemcpyAsync(h->hs_v2.p, d_v2, 8 * total, kd, cs));
         }
-        HIPCHK(h, hipMemcpyAsync(h->hs_key.p, h->s_key.p, 8 * total, kd, cs));
+        HIPCHK(h, hipMemcpyAsync(h->hs_key.p, d_key, 8 * total, kd, cs));
         HIPCHK(h, hipMemcpyAsync(h->hs_slice.p, h->s_slice.p, 8 * total, kd, cs));
-        HIPCHK(h, hipMemcpyAsync(h->hs_cs.p, h->s_cs.p, 8 * total, kd, cs));
+        HIPCHK(h, hipMemcpyAsync(h->hs_cs.p, d_cs, 8 * total, kd, cs));
         // no table counts NULL values: COUNT(v) = COUNT(*) for every entry, and the image's
         // cnt_val column is its cnt_star column (a fifth less to copy while the job runs on)
         bool any_null = false;
         for (auto& kv : h->tables) any_null = any_null || kv.second->has_null;
         h->snap_cv_alias = !any_null;
-        if (any_null) HIPCHK(h, hipMemcpyAsync(h->hs_cv.p, h->s_cv.p, 8 * total, kd, cs));
-        HIPCHK(h, hipMemcpyAsync(h->hs_sum.p, h->s_sum.p, 8 * total, kd, cs));
+        if (any_null) HIPCHK(h, hipMemcpyAsync(h->hs_cv.p, d_cv, 8 * total, kd, cs));
+        HIPCHK(h, hipMemcpyAsync(h->hs_sum.p, d_sum, 8 * total, kd, cs));
+        if (h->snap_grouped)   // the index travels with the image
+            HIPCHK(h, hipMemcpyAsync(h->hs_kg_off.p, h->kg_off.p, 4 * (size_t)(h->snap_bins + 1), kd, cs));
     }
     h->snap_pending = true;
     h->snap_total = total;
@@ -4319,7 +4401,35 @@ static int snapshot_end(fg_handle* h, fg_state_rows* out, int64_t* timer_waterma
     out->min = h->mv ? h->hs_v1.as<int64_t>() : nullptr;   // multi-value operators: the MIN / MAX slots
     out->max = h->mv ? h->hs_v2.as<int64_t>() : nullptr;
     if (timer_watermark) *timer_watermark = h->snap_wm;
+    if (h->snap_grouped) {   // the index: the scanned counters, widened (an image without rows: all 0)
+        h->img_kg_first.assign((size_t)h->snap_bins + 1, 0);
+        if (total > 0)
+            for (int64_t i = 0; i <= h->snap_bins; i++) h->img_kg_first[(size_t)i] = h->hs_kg_off.as<uint32_t>()[i];
+    }
     h->img_ready = true;
+    return FG_OK;
+}
+
+int fg_set_snapshot_grouping(fg_handle* h, int32_t key_hash) {
+    if (!h) return FG_EINVAL;
+    if (key_hash >= 0 && key_hash != FG_KEYHASH_BINARYROW_BIGINT && key_hash != FG_KEYHASH_JAVA_LONG &&
+        key_hash != FG_KEYHASH_DICT_ID)
+        return h->fail(FG_EINVAL, "fg_set_snapshot_grouping: unknown key_hash %d", key_hash);
+    if (key_hash >= 0 && (h->cfg.max_parallelism < 1 || h->cfg.max_parallelism > 32768))
+        return h->fail(FG_EINVAL, "fg_set_snapshot_grouping: max_parallelism %d is not in 1 .. 32768", h->cfg.max_parallelism);
+    if (h->snap_pending)
+        return h->fail(FG_EINVAL, "fg_set_snapshot_grouping: an asynchronous snapshot is not collected yet");
+    h->snap_group = key_hash < 0 ? -1 : key_hash;
+    return FG_OK;
+}
+
+int fg_snapshot_key_groups(fg_handle* h, fg_image_key_groups* out) {
+    if (!h || !out) return FG_EINVAL;
+    if (!h->img_ready) return h->fail(FG_ESTATE, "fg_snapshot_key_groups: no image returned since the last snapshot call");
+    if (!h->snap_grouped) return h->fail(FG_ESTATE, "fg_snapshot_key_groups: the image was taken with grouping off");
+    out->n_slices = (int64_t)h->img_se.size();
+    out->max_parallelism = h->cfg.max_parallelism;
+    out->first_row = h->img_kg_first.data();
     return FG_OK;
 }
 

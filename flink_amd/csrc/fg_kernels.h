@@ -620,4 +620,34 @@ hipError_t launch_rr_size(const uint32_t* hist, int32_t n_slices, uint32_t* out,
 hipError_t launch_rr_fold(const uint32_t* hist, int32_t n_slices, int32_t bits, uint32_t* cnt, hipStream_t s);
 hipError_t launch_rr_scatter(const RrParams& p, hipStream_t s);
 
+// ---- key-grouped snapshot image (fg_set_snapshot_grouping): the rows of every slice of the
+// exported device image reordered by key group, with the (slice, key group) row offsets ----
+//   k_kg_count    rows per (slice, key group) into cnt[s * max_p + g]
+//   (launch_scan_u32 over cnt: off[s * max_p + g] = the first image row of the run; the slices
+//   lie one after the other in the image, so the scan order is the final order)
+//   k_kg_scatter  the live columns into the second column set, every run reserved from cnt
+// Both give each workgroup one row segment (the k_rr_* walk) and walk the part of every slice in
+// it once per window of kKgWindow key groups, with one LDS counter per key group of the window:
+// global atomics are one per workgroup, slice and non-empty key group, never per row. A slice's
+// rows keep their slice, so the slice_end column stays where the export wrote it.
+constexpr int kKgWindow = 8192;               // LDS counters of a walk (32 KiB: five workgroups per CU)
+constexpr int kKgMaxCols = 6;                 // key, cnt_star, cnt_val, sum, min, max
+constexpr int64_t kKgMaxBins = (int64_t)1 << 30;   // slices x max_p
+struct KgParams {
+    const int64_t* key;          // the exported image's key column
+    int64_t n;                   // its rows (1 <= n < 2^32)
+    const int64_t* slice_first;  // device [n_slices + 1]: slice s holds rows [slice_first[s], slice_first[s + 1])
+    int32_t n_slices;
+    int32_t grid;                // rr_grid(n)
+    int32_t key_hash, max_p;     // key_group_of's arguments
+    uint32_t* cnt;               // [n_slices * max_p]: count adds to it (zeroed by the caller), scatter takes
+                                 // every run's positions back out of it (all zero again afterwards)
+    const uint32_t* off;         // scatter: [n_slices * max_p + 1] the exclusive scan of cnt
+    int32_t n_cols;              // scatter: columns to move (src[0] is `key`)
+    const int64_t* src[kKgMaxCols];
+    int64_t* dst[kKgMaxCols];
+};
+hipError_t launch_kg_count(const KgParams& p, hipStream_t s);
+hipError_t launch_kg_scatter(const KgParams& p, hipStream_t s);
+
 }  // namespace fg

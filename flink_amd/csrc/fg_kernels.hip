@@ -16,6 +16,8 @@
 //   k_key_groups / k_owner_*           KeyGroupRangeAssignment routing for the key-group exchange
 //   k_rr_*                             rescale restore: checkpoint images filtered by key-group range
 //                                      and grouped by (slice, region) for the merge
+//   k_kg_*                             key-grouped checkpoint image: every slice's exported rows
+//                                      ordered by key group, with the (slice, key group) offsets
 //
 // All global traffic is streaming and coalesced; per-key read-modify-write happens in LDS
 // (ds_cmpst_rtn_b64 / ds_add_u64 / ds_add_f64), never as global atomics.
@@ -3310,6 +3312,88 @@ hipError_t launch_rr_scatter(const RrParams& p, hipStream_t s) {
         (p.o_v1 != nullptr) != (p.o_v2 != nullptr))
         return hipErrorInvalidValue;
     fg_launch(k_rr_pass<true>, dim3(p.grid), dim3(kRrThreads), 0, s, p);
+    return hipGetLastError();
+}
+
+// ----------------------------------------------------------------------------------------
+// key-grouped snapshot image (fg_kernels.h): rows per (slice, key group), then the rows moved
+// ----------------------------------------------------------------------------------------
+// One workgroup per row segment. The host knows every slice's row range, so the workgroup finds
+// the slices of its segment by binary search and walks each one's part once per window of
+// kKgWindow key groups. Count: the LDS counters are added to cnt. Scatter: each non-empty
+// (slice, key group) takes its rows' positions back out of cnt (one global atomic; the run
+// starts at off), and a second walk moves the rows there.
+template <bool SCATTER>
+__global__ __launch_bounds__(kRrThreads) void k_kg_pass(KgParams p) {
+    __shared__ uint32_t s_h[kKgWindow];
+    const int tid = threadIdx.x;
+    int64_t beg, end;
+    seg_bounds(p.n, p.grid, blockIdx.x, &beg, &end);
+    if (beg >= end) return;   // (workgroup-uniform)
+    int lo = 0, hi = p.n_slices - 1;   // the first slice whose rows end after beg
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (gbl(p.slice_first)[mid + 1] <= beg) lo = mid + 1;
+        else hi = mid;
+    }
+    for (int s = lo; s < p.n_slices; s++) {
+        const int64_t f = gbl(p.slice_first)[s], l = gbl(p.slice_first)[s + 1];
+        if (f >= end) break;
+        const int64_t a = beg > f ? beg : f, b = end < l ? end : l;
+        if (a >= b) continue;   // (a slice without rows)
+        for (int w0 = 0; w0 < p.max_p; w0 += kKgWindow) {
+            const int nb = p.max_p - w0 < kKgWindow ? p.max_p - w0 : kKgWindow;
+            for (int r = tid; r < nb; r += kRrThreads) s_h[r] = 0;
+            __syncthreads();
+            for (int64_t i = a + tid; i < b; i += kRrThreads) {
+                const int g = key_group_of(gbl(p.key)[i], p.key_hash, p.max_p) - w0;
+                if ((unsigned)g < (unsigned)nb) atomicAdd(&s_h[g], 1u);
+            }
+            __syncthreads();
+            const int64_t bin0 = (int64_t)s * p.max_p + w0;
+            if constexpr (!SCATTER) {
+                for (int r = tid; r < nb; r += kRrThreads) {
+                    const uint32_t c = s_h[r];
+                    if (c) atomicAdd(&p.cnt[bin0 + r], c);
+                }
+            } else {
+                for (int r = tid; r < nb; r += kRrThreads) {
+                    const uint32_t c = s_h[r];
+                    if (c) s_h[r] = gbl(p.off)[bin0 + r] + (atomicSub(&p.cnt[bin0 + r], c) - c);
+                }
+                __syncthreads();
+                for (int64_t i = a + tid; i < b; i += kRrThreads) {
+                    const int64_t key = gbl(p.key)[i];
+                    const int g = key_group_of(key, p.key_hash, p.max_p) - w0;
+                    if ((unsigned)g >= (unsigned)nb) continue;
+                    const int64_t pos = (int64_t)atomicAdd(&s_h[g], 1u);
+                    if (pos < f || pos >= l) continue;   // (never: a run lies inside its slice)
+                    p.dst[0][pos] = key;
+#pragma unroll
+                    for (int c = 1; c < kKgMaxCols; c++)
+                        if (c < p.n_cols) p.dst[c][pos] = gbl(p.src[c])[i];
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+static bool kg_params_ok(const KgParams& p) {
+    return p.key != nullptr && p.n >= 1 && p.n < ((int64_t)1 << 32) && p.slice_first != nullptr && p.n_slices >= 1 &&
+           p.grid >= 1 && p.grid <= kRrMaxGrid && p.max_p >= 1 && (int64_t)p.n_slices * p.max_p <= kKgMaxBins &&
+           p.cnt != nullptr;
+}
+hipError_t launch_kg_count(const KgParams& p, hipStream_t s) {
+    if (!kg_params_ok(p)) return hipErrorInvalidValue;
+    fg_launch(k_kg_pass<false>, dim3(p.grid), dim3(kRrThreads), 0, s, p);
+    return hipGetLastError();
+}
+hipError_t launch_kg_scatter(const KgParams& p, hipStream_t s) {
+    if (!kg_params_ok(p) || !p.off || p.n_cols < 1 || p.n_cols > kKgMaxCols || p.src[0] != p.key) return hipErrorInvalidValue;
+    for (int c = 0; c < p.n_cols; c++)
+        if (!p.src[c] || !p.dst[c]) return hipErrorInvalidValue;
+    fg_launch(k_kg_pass<true>, dim3(p.grid), dim3(kRrThreads), 0, s, p);
     return hipGetLastError();
 }
 

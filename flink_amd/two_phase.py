@@ -370,3 +370,37 @@ def restore_union(glob, images, key_hash=None):
     entries of its own key groups (fg_restore_range). Returns the restore's info dict."""
     from . import _lib as L
     return glob.restore_state_range(images, None, L.KEYHASH_BINARYROW_BIGINT if key_hash is None else key_hash)
+
+
+def keyed_runs(image, index, key_group_range):
+    """The rows of a key-grouped image (WindowAggOperator.set_snapshot_grouping) whose key group
+    lies in key_group_range = (lo, hi): one contiguous run of rows per slice, found from `index`
+    (snapshot_key_groups) alone -- no key group is computed here, and no row outside the range is
+    touched (KeyGroupRangeOffsets: a restore reads the ranges it owns). Returns the non-empty runs
+    as image dicts of views into `image` (nothing is copied)."""
+    maxp, first = int(index["max_parallelism"]), index["first_row"]
+    lo, hi = max(int(key_group_range[0]), 0), min(int(key_group_range[1]), maxp - 1)
+    if lo > hi:
+        return []
+    runs = [(int(first[s * maxp + lo]), int(first[s * maxp + hi + 1])) for s in range(int(index["n_slices"]))]
+    return [{c: v[a:b] for c, v in image.items()} for a, b in runs if b > a]
+
+
+def keyed_part(image, index, key_group_range):
+    """keyed_runs as one image dict: the rows of the range, slice by slice (a copy when the range
+    has rows in several slices)."""
+    runs = keyed_runs(image, index, key_group_range)
+    if len(runs) == 1:
+        return runs[0]
+    return {c: (np.concatenate([r[c] for r in runs]) if runs else v[:0]) for c, v in image.items()}
+
+
+def restore_keyed(glob, sources):
+    """restore_union for key-grouped images: sources = [(image, timer watermark, index), ...] of
+    every old subtask. The global operator `glob` takes, out of every image, only the runs of its
+    own key-group range (keyed_runs; they are handed over as they lie, one image per run) and
+    restores them with the minimum watermark (restore_state_range: rows_in == rows_kept when the
+    images were grouped with its hash). Returns the restore's info dict."""
+    rng = (glob.cfg.key_group_start, glob.cfg.key_group_end)
+    parts = [run for img, _, idx in sources for run in keyed_runs(img, idx, rng)]
+    return glob.restore_state_range(parts, min(int(wm) for _, wm, _ in sources))

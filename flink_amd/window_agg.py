@@ -505,6 +505,24 @@ class WindowAggOperator:
         return dict(slice_end=col(s.slice_end, C.c_int64, np.int64), first_row=col(s.first_row, C.c_int64, np.int64),
                     rows=col(s.rows, C.c_int64, np.int64), changed=col(s.changed, C.c_uint8, np.uint8).astype(bool))
 
+    def set_snapshot_grouping(self, key_hash=L.KEYHASH_BINARYROW_BIGINT):
+        """fg_set_snapshot_grouping: from the next snapshot on, the rows of every slice of an image
+        are ordered by key group (of `key_hash` and this operator's max_parallelism), partitioned
+        on the GPU before the image leaves it; snapshot_key_groups returns the offsets. None turns
+        the grouping off."""
+        L.check(self._lib.fg_set_snapshot_grouping(self._h, -1 if key_hash is None else int(key_hash)), self._h)
+
+    def snapshot_key_groups(self) -> dict:
+        """fg_snapshot_key_groups: the index of the grouped image the last snapshot returned --
+        n_slices (the slices of snapshot_slices, same order), max_parallelism, and first_row
+        (int64, n_slices * max_parallelism + 1): key group g of slice s holds the image rows
+        [first_row[s * max_parallelism + g], first_row[s * max_parallelism + g + 1])."""
+        k = L.FgImageKeyGroups()
+        L.check(self._lib.fg_snapshot_key_groups(self._h, C.byref(k)), self._h)
+        n = int(k.n_slices) * int(k.max_parallelism) + 1
+        first = np.ctypeslib.as_array(C.cast(k.first_row, C.POINTER(C.c_int64)), shape=(n,)).copy()
+        return dict(n_slices=int(k.n_slices), max_parallelism=int(k.max_parallelism), first_row=first)
+
     def restore_state(self, image, timer_watermark: int):
         names = ("key", "slice_end", "cnt_star", "cnt_val", "sum") + (("min", "max") if "min" in image else ())
         cols = {k: np.ascontiguousarray(image[k], dtype=np.int64) for k in names}

@@ -27,6 +27,8 @@
  *   AbstractStreamOperator.initializeState after a rescale: KeyGroupRangeAssignment /
  *     StateAssignmentOperation (each new subtask takes its key-group range out of every
  *     old subtask's state)                                                fg_restore_range
+ *   HeapSnapshotStrategy / KeyGroupRangeOffsets (a keyed snapshot written in key-group order
+ *     with an offset per key group)                  fg_set_snapshot_grouping, fg_snapshot_key_groups
  *   SlicingWindowOperator.getNumLateRecordsDropped :300-303            fg_late_dropped
  *   two-phase: LocalAggCombiner.combine (local operator output)        fg_config.flags |= FG_FLAG_LOCAL_PARTIALS
  *     GlobalAggCombiner.combine  .../combines/GlobalAggCombiner.java:77-110  fg_add_partials
@@ -358,6 +360,38 @@ typedef struct fg_image_slices {
     const uint8_t* changed;     /* [n] 1 / 0 */
 } fg_image_slices;
 int  fg_snapshot_slices(fg_handle* h, fg_image_slices* out);
+/* Key-grouped images (ABI 16, added; Flink writes a keyed snapshot in key-group order with an offset
+ * per key group -- KeyGroupRangeOffsets, HeapSnapshotStrategy -- so that a restore after a rescale
+ * reads only the ranges it owns). From the next snapshot on, the rows of every slice of an image are
+ * ordered by key group (key_group(key, key_hash, fg_config.max_parallelism)), ascending; key_hash < 0
+ * turns the grouping off (the default).
+ *  - A grouped image is a valid fg_snapshot_state image in every respect: the same multiset of rows,
+ *    the same slice grouping and the same fg_snapshot_slices answer. Only the order of the rows inside
+ *    a slice differs; the order inside one (slice, key group) run is unspecified.
+ *  - Works with fg_snapshot_state and with _async / _wait (the image is the state as of the _async
+ *    call). The partition runs as kernels on the handle's stream between the export and the image's
+ *    device-to-host copy; the host reads no row. A cnt_val column that aliases cnt_star (see
+ *    fg_snapshot_state_async) is neither moved nor copied.
+ *  - FG_EINVAL: a key_hash >= 0 that is no fg_key_hash; a handle whose max_parallelism is not in
+ *    1 .. 32768; an asynchronous snapshot not collected yet. The call does no device work, and the
+ *    handle stays usable after an error.
+ *  - Extra device memory while the grouping is on: one more set of the moved image columns, 8 B x
+ *    (3 .. 6: key, cnt_star, sum, and cnt_val / min / max where the image has them; slice_end stays in
+ *    place) per row, and 8 B x max_parallelism x slices for the (slice, key group) counters and their
+ *    offsets.
+ * fg_snapshot_key_groups: the index of the image the last fg_snapshot_state / _wait returned, valid
+ * as long as fg_snapshot_slices' answer. FG_ESTATE if no image was returned since the last snapshot
+ * call, or if that image was taken with the grouping off. An image without slices: n_slices == 0 and
+ * first_row == {0}. first_row[s * max_parallelism] == fg_image_slices.first_row[s], and the last
+ * entry is the image's row count. */
+int  fg_set_snapshot_grouping(fg_handle* h, int32_t key_hash);
+typedef struct fg_image_key_groups {
+    int64_t n_slices;            /* = fg_image_slices.n of the same image, same order */
+    int32_t max_parallelism;     /* key groups per slice */
+    const int64_t* first_row;    /* [n_slices * max_parallelism + 1]: key group g of slice s holds image
+                                  * rows [first_row[s*maxp+g], first_row[s*maxp+g+1]) */
+} fg_image_key_groups;
+int  fg_snapshot_key_groups(fg_handle* h, fg_image_key_groups* out);
 /* The device self-check (ABI 16): the DPP wave scans and the tile walk the fire runs, as this
  * library's code object compiled them, on inputs whose answers the host knows (msg: "ok" or what is
  * wrong). fg_open runs it once per process and device and fails with FG_EDEVICE (its message in

@@ -116,6 +116,20 @@ public final class FlinkGpu {
      */
     public static native long[] snapshotSlices(long h);
 
+    /**
+     * fg_set_snapshot_grouping: from the next snapshot on, the rows of every slice of an image are
+     * ordered by key group (keyHash, the handle's max parallelism), partitioned on the GPU before
+     * the image leaves it; keyHash &lt; 0 turns the grouping off.
+     */
+    public static native void snapshotGrouping(long h, int keyHash);
+
+    /**
+     * fg_snapshot_key_groups: the index of the grouped image the last snapshotState /
+     * snapshotStateWait returned, as [nSlices, maxP, firstRow[nSlices * maxP + 1]]: key group g of
+     * slice s holds the image rows [firstRow[s * maxP + g], firstRow[s * maxP + g + 1]).
+     */
+    public static native long[] snapshotKeyGroups(long h);
+
     /** fg_restore. */
     public static native void restore(
             long h,

@@ -157,6 +157,8 @@ public final class GpuTwoPhaseWindowAggOperator extends TableStreamOperator<RowD
                         FgConfig.of(spec, maxP, range.getStartKeyGroup(), range.getEndKeyGroup(), nTz),
                         spec.tzTransitionsMs,
                         spec.tzOffsetsMs);
+        // the global's images leave the GPU ordered by key group: a restore reads only its own chunks
+        FlinkGpu.snapshotGrouping(global, FlinkGpu.KEYHASH_BINARYROW_BIGINT);
         keys = new GpuKeyRows(spec, maxP);
         accRows = new GpuAccRows(spec.aggs, spec.valType);
         int b = spec.batchRecords;
@@ -504,38 +506,66 @@ public final class GpuTwoPhaseWindowAggOperator extends TableStreamOperator<RowD
 
     // ---- the image as union operator state --------------------------------------------------------
 
-    /** the global's image (snapshotStateAsync + Wait) as chunks: [n, timer wm, n x 7 longs] each */
+    /**
+     * the global's image (snapshotStateAsync + Wait), grouped by key group on the GPU
+     * (snapshotGrouping), as chunks cut along key-group boundaries: [rows, timer wm, kgLo, kgHi,
+     * rows x 7 longs] each. A chunk lies inside one slice and holds whole key groups kgLo .. kgHi
+     * of it (a key group larger than a chunk is split into chunks of that one key group), so a
+     * restore decodes only the chunks whose key groups it owns.
+     */
     private byte[][] imageChunks() {
         FlinkGpu.snapshotStateAsync(global);
         ByteBuffer[] cols = new ByteBuffer[7];
         long[] wm = new long[1];
-        int n = (int) FlinkGpu.snapshotStateWait(global, cols, wm);
+        FlinkGpu.snapshotStateWait(global, cols, wm);
         for (ByteBuffer c : cols) {
             if (c != null) {
                 c.order(ByteOrder.nativeOrder());
             }
         }
-        int chunks = Math.max(1, (n + IMAGE_CHUNK_ROWS - 1) / IMAGE_CHUNK_ROWS);
-        byte[][] out = new byte[chunks][];
-        for (int k = 0; k < chunks; k++) {
-            int lo = k * IMAGE_CHUNK_ROWS, hi = Math.min(n, lo + IMAGE_CHUNK_ROWS);
-            ByteBuffer b = ByteBuffer.allocate(16 + 56 * (hi - lo)).order(ByteOrder.LITTLE_ENDIAN);
-            b.putLong(hi - lo).putLong(wm[0]);
-            for (int i = lo; i < hi; i++) {
-                for (int c = 0; c < 7; c++) {
-                    ByteBuffer col = cols[c] != null ? cols[c] : cols[4];   // (min / max: single-value lists)
-                    b.putLong(col.getLong(8 * i));
-                }
+        long[] kg = FlinkGpu.snapshotKeyGroups(global);   // [slices, maxP, firstRow...]
+        int bins = (int) (kg[0] * kg[1]), mp = (int) kg[1];
+        List<byte[]> out = new ArrayList<>();
+        int g = 0;
+        while (g < bins) {
+            long lo = kg[2 + g];
+            int first = g, sliceEnd = (g / mp + 1) * mp;   // (bins of this slice end here)
+            g++;
+            while (g < sliceEnd && kg[2 + g + 1] - lo <= IMAGE_CHUNK_ROWS) {
+                g++;
             }
-            out[k] = b.array();
+            long hi = kg[2 + g];
+            if (hi == lo) {
+                continue;   // (a run of empty key groups)
+            }
+            for (long at = lo; at < hi; at += IMAGE_CHUNK_ROWS) {   // (several only for one large key group)
+                out.add(chunk(cols, at, Math.min(hi, at + IMAGE_CHUNK_ROWS), wm[0], first % mp, (g - 1) % mp));
+            }
         }
-        return out;
+        if (out.isEmpty()) {
+            out.add(chunk(cols, 0, 0, wm[0], 0, -1));   // (the timer watermark of an empty image)
+        }
+        return out.toArray(new byte[0][]);
+    }
+
+    private static byte[] chunk(ByteBuffer[] cols, long lo, long hi, long wm, int kgLo, int kgHi) {
+        ByteBuffer b = ByteBuffer.allocate(32 + 56 * (int) (hi - lo)).order(ByteOrder.LITTLE_ENDIAN);
+        b.putLong(hi - lo).putLong(wm).putLong(kgLo).putLong(kgHi);
+        for (long i = lo; i < hi; i++) {
+            for (int c = 0; c < 7; c++) {
+                ByteBuffer col = cols[c] != null ? cols[c] : cols[4];   // (min / max: single-value lists)
+                b.putLong(col.getLong((int) (8 * i)));
+            }
+        }
+        return b.array();
     }
 
     /**
-     * initializeState: every subtask's chunks decoded straight into seven direct column buffers;
-     * the global handle, opened with this subtask's key-group range, keeps the entries of its own
-     * key groups on the GPU (fg_restore_range). A subtask that owns every key group keeps them all.
+     * initializeState: every chunk's header is read (the timer watermark is the minimum over all
+     * of them), and only the chunks whose key groups [kgLo, kgHi] intersect this subtask's range are
+     * decoded into the seven direct column buffers. If every decoded chunk lies inside the range,
+     * they are the subtask's state as they are (fg_restore); else the global handle, opened with the
+     * range, drops the foreign rows of the boundary chunks on the GPU (fg_restore_range).
      */
     private void restoreGlobal(KeyGroupRange range) {
         if (restoredImage == null || restoredImage.isEmpty()) {
@@ -543,10 +573,19 @@ public final class GpuTwoPhaseWindowAggOperator extends TableStreamOperator<RowD
         }
         long timerWm = Long.MAX_VALUE;
         long total = 0;
+        boolean inside = true;
+        List<ByteBuffer> mine = new ArrayList<>();
         for (byte[] chunk : restoredImage) {
             ByteBuffer b = ByteBuffer.wrap(chunk).order(ByteOrder.LITTLE_ENDIAN);
-            total += b.getLong();
+            long rows = b.getLong();
             timerWm = Math.min(timerWm, b.getLong());
+            long kgLo = b.getLong(), kgHi = b.getLong();
+            if (rows == 0 || kgHi < range.getStartKeyGroup() || kgLo > range.getEndKeyGroup()) {
+                continue;
+            }
+            inside &= kgLo >= range.getStartKeyGroup() && kgHi <= range.getEndKeyGroup();
+            total += rows;
+            mine.add(b);
         }
         int n = Math.toIntExact(total);
         ByteBuffer[] c = new ByteBuffer[7];
@@ -554,10 +593,8 @@ public final class GpuTwoPhaseWindowAggOperator extends TableStreamOperator<RowD
             c[j] = GpuKeyRows.direct(8L * Math.max(n, 1));
         }
         int at = 0;
-        for (byte[] chunk : restoredImage) {
-            ByteBuffer b = ByteBuffer.wrap(chunk).order(ByteOrder.LITTLE_ENDIAN);
-            long rows = b.getLong();
-            b.getLong();
+        for (ByteBuffer b : mine) {
+            long rows = b.getLong(0);
             for (long i = 0; i < rows; i++, at++) {
                 for (int j = 0; j < 7; j++) {
                     c[j].putLong(8 * at, b.getLong());
@@ -566,7 +603,7 @@ public final class GpuTwoPhaseWindowAggOperator extends TableStreamOperator<RowD
         }
         boolean mv = accRows.multiValue();
         ByteBuffer min = mv ? c[5] : null, max = mv ? c[6] : null;
-        if (range.getNumberOfKeyGroups() == maxP) {
+        if (inside) {
             FlinkGpu.restore(global, n, c[0], c[1], c[2], c[3], c[4], min, max, timerWm);
         } else {
             FlinkGpu.restoreRange(

@@ -25,6 +25,8 @@
  *   hostRegister    fg_host_register     (page-lock a managed-memory segment at open: direct DMA)
  *   hostUnregister  fg_host_unregister   (at close)
  *   snapshotSlices  fg_snapshot_slices   (the image's slices and which changed: the incremental keyed-state write)
+ *   snapshotGrouping / snapshotKeyGroups   fg_set_snapshot_grouping / fg_snapshot_key_groups (images ordered
+ *                   by key group inside every slice, and the offsets: chunks cut along key groups)
  *   comm*           fg_comm_*            (the keyBy edge local -> global over RCCL: KeyGroupStreamPartitioner
  *                                         + RecordWriter + StatusWatermarkValve between co-located subtasks;
  *                                         commRoundBegin / Exchange / End: a round on the subtask's edge thread)
@@ -334,6 +336,32 @@ JNIEXPORT jlongArray JNICALL FN(snapshotSlices)(JNIEnv* env, jclass cls, jlong h
     }
     (*env)->SetLongArrayRegion(env, out, 0, 1 + 4 * n, buf);
     free(buf);
+    return out;
+}
+
+/* void snapshotGrouping(long h, int keyHash): from the next snapshot on, every slice's rows of an image
+ * are ordered by key group (fg_set_snapshot_grouping; keyHash < 0: off) */
+JNIEXPORT void JNICALL FN(snapshotGrouping)(JNIEnv* env, jclass cls, jlong hp, jint keyHash) {
+    (void)cls;
+    fg_handle* h = (fg_handle*)(intptr_t)hp;
+    (void)check(env, h, fg_set_snapshot_grouping(h, keyHash));
+}
+
+/* long[] snapshotKeyGroups(long h): the index of the grouped image the last snapshotState /
+ * snapshotStateWait returned (fg_snapshot_key_groups) as one array: [n_slices, maxp,
+ * first_row[n_slices * maxp + 1]] -- key group g of slice s holds the image rows
+ * [first_row[s * maxp + g], first_row[s * maxp + g + 1]) */
+JNIEXPORT jlongArray JNICALL FN(snapshotKeyGroups)(JNIEnv* env, jclass cls, jlong hp) {
+    (void)cls;
+    fg_handle* h = (fg_handle*)(intptr_t)hp;
+    fg_image_key_groups k;
+    if (check(env, h, fg_snapshot_key_groups(h, &k))) return NULL;
+    const jsize n = (jsize)(k.n_slices * k.max_parallelism + 1);
+    jlongArray out = (*env)->NewLongArray(env, 2 + n);
+    if (!out) return NULL;
+    const jlong head[2] = {k.n_slices, k.max_parallelism};
+    (*env)->SetLongArrayRegion(env, out, 0, 2, head);
+    (*env)->SetLongArrayRegion(env, out, 2, n, (const jlong*)k.first_row);
     return out;
 }
 
