@@ -4465,130 +4465,6 @@ int fg_snapshot_state(fg_handle* h, fg_state_rows* out, int64_t* timer_watermark
     return snapshot_end(h, out, timer_watermark);
 }
 
-static int restore_finish(fg_handle* h, int64_t timer_watermark, bool was_empty);
-
-int fg_restore(fg_handle* h, const fg_state_rows* in, int64_t timer_watermark) {
-    if (!h || !in) return FG_EINVAL;
-    const bool was_empty = h->tables.empty();   // (restored into a new handle: its tables equal the image)
-    h->cnt_bound = JMAX;
-    h->keys32 = false;
-    HIPCHK(h, hipSetDevice(h->device));
-    if (int rc0 = settle_pending(h)) return rc0;
-    int rc = flush(h);
-    if (rc) return rc;
-    // group entries by slice, bucket by region on the host (restore is off the hot path)
-    std::map<int64_t, std::vector<int64_t>> by_slice;
-    for (int64_t i = 0; i < in->n; i++) by_slice[in->slice_end[i]].push_back(i);
-    // regions sized for the image first: the smallest split whose fullest region keeps the
-    // LDS tables at most ~70 % full (a slice restored into a live table may still split more)
-    {
-        int need = h->region_bits;
-        for (auto& kv : by_slice) {
-            std::vector<uint32_t> c13((size_t)1 << kMaxRegionBits, 0);
-            for (int64_t i : kv.second) c13[fmix64((uint64_t)in->key[i]) >> (64 - kMaxRegionBits)]++;
-            for (int b = need; b <= kMaxRegionBits; b++) {
-                uint32_t mx = 0;
-                const int per = 1 << (kMaxRegionBits - b);
-                for (size_t r = 0; r < c13.size(); r += (size_t)per) {
-                    uint32_t sum = 0;
-                    for (int c = 0; c < per; c++) sum += c13[r + (size_t)c];
-                    mx = std::max(mx, sum);
-                }
-                need = b;
-                if (mx <= (uint32_t)(0.7 * h->tcap)) break;
-            }
-        }
-        rc = grow(h, need);
-        if (rc) return rc;
-    }
-    for (auto& kv : by_slice) {
-        const auto& idx = kv.second;
-        const int64_t m = (int64_t)idx.size();
-        const int NB = 1 << h->region_bits;
-        std::vector<uint32_t> off(NB + 1, 0);
-        std::vector<uint32_t> reg(m);
-        for (int64_t j = 0; j < m; j++) {
-            const uint64_t hk = fmix64((uint64_t)in->key[idx[j]]);
-            reg[j] = h->region_bits == 0 ? 0u : (uint32_t)(hk >> (64 - h->region_bits));
-            off[reg[j] + 1]++;
-        }
-        for (int r = 0; r < NB; r++) off[r + 1] += off[r];
-        if (h->mv && (!in->min || !in->max))
-            return h->fail(FG_EINVAL, "a multi-value operator's image needs the min and max columns");
-        std::vector<int64_t> k(m), cs(m), cn(m), sm(m), v1(h->mv ? m : 0), v2(h->mv ? m : 0);
-        std::vector<uint32_t> cur(off.begin(), off.end() - 1);
-        for (int64_t j = 0; j < m; j++) {
-            const int64_t i = idx[j];
-            const uint32_t at = cur[reg[j]]++;
-            k[at] = mix_of(in->key[i]);   // state keeps the key's mix (fg_window.h)
-            cs[at] = in->cnt_star[i];
-            cn[at] = in->cnt_star[i] - in->cnt_val[i];
-            sm[at] = in->sum[i];
-            if (h->mv) {
-                v1[at] = in->min[i];
-                v2[at] = in->max[i];
-            }
-        }
-        DevBuf dk, dcs, dcn, dsm, doff, dv1, dv2;
-        if (h->mv) {
-            HIPCHK(h, dv1.ensure(8 * std::max<int64_t>(m, 1)));
-            HIPCHK(h, dv2.ensure(8 * std::max<int64_t>(m, 1)));
-            HIPCHK(h, hipMemcpy(dv1.p, v1.data(), 8 * m, hipMemcpyHostToDevice));
-            HIPCHK(h, hipMemcpy(dv2.p, v2.data(), 8 * m, hipMemcpyHostToDevice));
-        }
-        HIPCHK(h, dk.ensure(8 * std::max<int64_t>(m, 1)));
-        HIPCHK(h, dcs.ensure(8 * std::max<int64_t>(m, 1)));
-        HIPCHK(h, dcn.ensure(8 * std::max<int64_t>(m, 1)));
-        HIPCHK(h, dsm.ensure(8 * std::max<int64_t>(m, 1)));
-        HIPCHK(h, doff.ensure(4 * (NB + 1)));
-        HIPCHK(h, hipMemcpy(dk.p, k.data(), 8 * m, hipMemcpyHostToDevice));
-        HIPCHK(h, hipMemcpy(dcs.p, cs.data(), 8 * m, hipMemcpyHostToDevice));
-        HIPCHK(h, hipMemcpy(dcn.p, cn.data(), 8 * m, hipMemcpyHostToDevice));
-        HIPCHK(h, hipMemcpy(dsm.p, sm.data(), 8 * m, hipMemcpyHostToDevice));
-        HIPCHK(h, hipMemcpy(doff.p, off.data(), 4 * (NB + 1), hipMemcpyHostToDevice));
-        SliceTable* t = nullptr;
-        rc = table_get(h, kv.first, true, &t);
-        if (rc) return rc;
-        MergeJob j;
-        JobBatch jb;
-        jb.ext.rec = dk.as<int64_t>();
-        jb.ext.stride = 1;
-        jb.ext.val = dsm.as<int64_t>();
-        jb.ext.cnt_star = dcs.as<int64_t>();
-        jb.ext.cnt_null = dcn.as<int64_t>();
-        jb.ext.bucket_off = doff.as<uint32_t>();
-        jb.ext.is_acc = 1;
-        jb.ext.val1 = dv1.as<int64_t>();
-        jb.ext.val2 = dv2.as<int64_t>();
-        jb.ext_bits = h->region_bits;
-        j.batches.push_back(jb);
-        j.srcs.push_back(t);
-        j.dst = t;
-        j.kclass = K_RESTORE;
-        if (int rc0 = zero_scalars(h, true)) return rc0;
-        int ji = 0;
-        rc = job_add(h, std::move(j), &ji);
-        if (rc) return rc;
-        MergeParams p{};
-        rc = job_params(h, ji, &p);
-        if (rc) return rc;
-        {
-            KTimer kt(h, K_RESTORE, m);
-            HIPCHK(h, launch_merge(p, merge_grid(h), h->stream));
-        }
-        HIPCHK(h, hipMemcpyAsync(h->h_scalars.p, h->scalars.p, kScalarBytes, hipMemcpyDeviceToHost, h->stream));
-        rc = sync(h);
-        if (rc) return rc;
-        rc = settle_jobs(h);   // the device buffers above stay alive until this returns
-        if (rc) return rc;
-        rc = check_overflow(h);
-        if (rc) return rc;
-        t->upper = std::min<int64_t>(t->upper + m, kStateCapMax);
-        t->changed = true;
-    }
-    return restore_finish(h, timer_watermark, was_empty);
-}
-
 // What a restore leaves besides the slice tables (fg_restore, fg_restore_range): progress, timer
 // watermark, re-fire and lateness horizons, the `changed` flags.
 static int restore_finish(fg_handle* h, int64_t timer_watermark, bool was_empty) {
@@ -4631,11 +4507,50 @@ static int restore_finish(fg_handle* h, int64_t timer_watermark, bool was_empty)
     return FG_OK;
 }
 
-// The rows of fg_restore_range's images that fall into the handle's key-group range, merged into
-// the slice tables: the filter, the grouping by (slice, region) and the scatter are kernels
-// (fg_kernels.h, k_rr_*); the host reads the slice dictionary and per-slice sizes, never a row.
-static int restore_range_rows(fg_handle* h, const fg_state_rows* images, int32_t n_images, int32_t location,
-                              int32_t key_hash, int64_t N, fg_restore_info* ri) {
+// One K_RESTORE merge: the `m` rows of a restore batch that belong to the slice ending at
+// `slice_end` (`seg`: their segment of the batch's columns, bucketed into 2^bits regions) into that
+// slice's table. The batch must stay alive until this returns (settle_jobs).
+static int restore_merge_slice(fg_handle* h, int64_t slice_end, const StagedBatch& seg, int bits, int64_t m) {
+    SliceTable* t = nullptr;
+    int rc = table_get(h, slice_end, true, &t);
+    if (rc) return rc;
+    MergeJob j;
+    JobBatch jb;
+    jb.ext = seg;
+    jb.ext_bits = bits;
+    j.batches.push_back(jb);
+    j.srcs.push_back(t);
+    j.dst = t;
+    j.kclass = K_RESTORE;
+    if (int rc0 = zero_scalars(h, true)) return rc0;
+    int ji = 0;
+    rc = job_add(h, std::move(j), &ji);
+    if (rc) return rc;
+    MergeParams mp{};
+    rc = job_params(h, ji, &mp);
+    if (rc) return rc;
+    {
+        KTimer kt(h, K_RESTORE, m);
+        HIPCHK(h, launch_merge(mp, merge_grid(h), h->stream));
+    }
+    HIPCHK(h, hipMemcpyAsync(h->h_scalars.p, h->scalars.p, kScalarBytes, hipMemcpyDeviceToHost, h->stream));
+    rc = sync(h);
+    if (rc) return rc;
+    rc = settle_jobs(h);
+    if (rc) return rc;
+    rc = check_overflow(h);
+    if (rc) return rc;
+    t->upper = std::min<int64_t>(t->upper + m, kStateCapMax);
+    t->changed = true;
+    return FG_OK;
+}
+
+// The rows of the images (N > 0 in all) merged into the slice tables -- with `filter`, only those
+// whose key group (`key_hash`) falls into the handle's range. The filter, the grouping by (slice,
+// region) and the scatter are kernels (fg_kernels.h, k_rr_*); the host reads the slice
+// dictionary and per-slice sizes, never a row. `fn`: the entry point, for messages.
+static int restore_rows(fg_handle* h, const char* fn, const fg_state_rows* images, int32_t n_images, int32_t location,
+                        bool filter, int32_t key_hash, int64_t N, fg_restore_info* ri) {
     const int ncols = h->mv ? 7 : 5;
     std::vector<RrImage> desc;
     DevBuf up;   // FG_HOST: the images' columns, one after the other over the concatenated rows
@@ -4676,10 +4591,12 @@ static int restore_range_rows(fg_handle* h, const fg_state_rows* images, int32_t
     p.n_images = (int32_t)desc.size();
     p.grid = rr_grid(N);
     p.n = N;
-    p.key_hash = key_hash;
-    p.max_p = h->cfg.max_parallelism;
-    p.kg_lo = h->cfg.key_group_start;
-    p.kg_hi = h->cfg.key_group_end;
+    if (filter) {   // (else max_p = 0: every row is kept, whatever the handle's key groups)
+        p.key_hash = key_hash;
+        p.max_p = h->cfg.max_parallelism;
+        p.kg_lo = h->cfg.key_group_start;
+        p.kg_hi = h->cfg.key_group_end;
+    }
     p.dict = d_dict.as<unsigned long long>();
     p.dict_n = reinterpret_cast<uint32_t*>(d_dict.as<unsigned long long>() + kRrDictSlots);
     {
@@ -4693,14 +4610,14 @@ static int restore_range_rows(fg_handle* h, const fg_state_rows* images, int32_t
     uint32_t dn[4];
     std::memcpy(dn, &hd[kRrDictSlots], sizeof dn);
     if ((int64_t)dn[0] + (dn[1] ? 1 : 0) > kRrMaxSlices)
-        return h->fail(FG_EINVAL, "fg_restore_range: more than %d distinct slice ends in one call", kRrMaxSlices);
+        return h->fail(FG_EINVAL, "%s: more than %d distinct slice ends in one call", fn, kRrMaxSlices);
     std::vector<int64_t> slices;
     for (int i = 0; i < kRrDictSlots; i++)
         if (hd[i] != kRrDictEmpty) slices.push_back((int64_t)hd[i]);
     if (dn[1]) slices.push_back((int64_t)kRrDictEmpty);
     std::sort(slices.begin(), slices.end());
     const int32_t S = (int32_t)slices.size();
-    if (S < 1 || S > kRrMaxSlices) return h->fail(FG_EDEVICE, "internal: fg_restore_range slice dictionary of %d", S);
+    if (S < 1 || S > kRrMaxSlices) return h->fail(FG_EDEVICE, "internal: %s slice dictionary of %d", fn, S);
     // kept rows per (slice, 13 region bits), and from them the fullest region of every split
     DevBuf d_sl, d_hist, d_size;
     HIPCHK(h, d_sl.ensure(8 * (size_t)S));
@@ -4720,8 +4637,8 @@ static int restore_range_rows(fg_handle* h, const fg_state_rows* images, int32_t
     HIPCHK(h, hipMemcpyAsync(sz.data(), d_size.p, 4 * sz.size(), hipMemcpyDeviceToHost, h->stream));
     rc = sync(h);
     if (rc) return rc;
-    // regions sized for the kept rows by fg_restore's rule: the smallest split whose fullest
-    // region keeps the LDS tables at most ~70 % full
+    // regions sized for the kept rows first: the smallest split whose fullest region keeps the
+    // LDS tables at most ~70 % full (a slice restored into a live table may still split more)
     int need = h->region_bits;
     int64_t kept = 0, live = 0;
     for (int32_t s = 0; s < S; s++) {
@@ -4767,54 +4684,68 @@ static int restore_range_rows(fg_handle* h, const fg_state_rows* images, int32_t
         HIPCHK(h, hipMemcpyAsync(d_cur.p, d_off.p, 4 * (size_t)F, hipMemcpyDeviceToDevice, h->stream));
         HIPCHK(h, launch_rr_scatter(p, h->stream));
     }
-    // one K_RESTORE merge per slice over its segment of the batch (which lives until the last
-    // settle_jobs below)
+    // one K_RESTORE merge per slice over its segment of the batch
     int64_t at = 0;
     for (int32_t s = 0; s < S; s++) {
         const int64_t m = sz[(size_t)s * kRrSizeCols];
         if (m == 0) continue;
-        SliceTable* t = nullptr;
-        rc = table_get(h, slices[s], true, &t);
+        StagedBatch seg{};
+        seg.rec = p.o_key + at;
+        seg.stride = 1;
+        seg.val = p.o_sum + at;
+        seg.cnt_star = p.o_cs + at;
+        seg.cnt_null = p.o_cn + at;
+        seg.bucket_off = d_off.as<uint32_t>() + (int64_t)s * NB;
+        seg.is_acc = 1;
+        seg.val1 = h->mv ? p.o_v1 + at : nullptr;
+        seg.val2 = h->mv ? p.o_v2 + at : nullptr;
+        rc = restore_merge_slice(h, slices[s], seg, bits, m);
         if (rc) return rc;
-        MergeJob j;
-        JobBatch jb;
-        jb.ext.rec = p.o_key + at;
-        jb.ext.stride = 1;
-        jb.ext.val = p.o_sum + at;
-        jb.ext.cnt_star = p.o_cs + at;
-        jb.ext.cnt_null = p.o_cn + at;
-        jb.ext.bucket_off = d_off.as<uint32_t>() + (int64_t)s * NB;
-        jb.ext.is_acc = 1;
-        jb.ext.val1 = h->mv ? p.o_v1 + at : nullptr;
-        jb.ext.val2 = h->mv ? p.o_v2 + at : nullptr;
-        jb.ext_bits = bits;
-        j.batches.push_back(jb);
-        j.srcs.push_back(t);
-        j.dst = t;
-        j.kclass = K_RESTORE;
-        if (int rc0 = zero_scalars(h, true)) return rc0;
-        int ji = 0;
-        rc = job_add(h, std::move(j), &ji);
-        if (rc) return rc;
-        MergeParams mp{};
-        rc = job_params(h, ji, &mp);
-        if (rc) return rc;
-        {
-            KTimer kt(h, K_RESTORE, m);
-            HIPCHK(h, launch_merge(mp, merge_grid(h), h->stream));
-        }
-        HIPCHK(h, hipMemcpyAsync(h->h_scalars.p, h->scalars.p, kScalarBytes, hipMemcpyDeviceToHost, h->stream));
-        rc = sync(h);
-        if (rc) return rc;
-        rc = settle_jobs(h);
-        if (rc) return rc;
-        rc = check_overflow(h);
-        if (rc) return rc;
-        t->upper = std::min<int64_t>(t->upper + m, kStateCapMax);
-        t->changed = true;
         at += m;
     }
     return FG_OK;
+}
+
+// The one restore body (fg_restore: one host image, no filter; fg_restore_range): the images' rows
+// merged into the slice tables on the GPU, then what restore_finish leaves. Argument errors are
+// reported before any device work, and leave the handle as it was.
+static int restore_images(fg_handle* h, const char* fn, const fg_state_rows* images, int32_t n_images, int32_t location,
+                          bool filter, int32_t key_hash, int64_t timer_watermark, fg_restore_info* info) {
+    int64_t N = 0;
+    for (int32_t g = 0; g < n_images; g++) {
+        const fg_state_rows& im = images[g];
+        if (im.n < 0) return h->fail(FG_EINVAL, "%s: image %d has %lld rows", fn, g, (long long)im.n);
+        if (im.n == 0) continue;
+        if (!im.key || !im.slice_end || !im.cnt_star || !im.cnt_val || !im.sum)
+            return h->fail(FG_EINVAL, "%s: image %d lacks a column", fn, g);
+        if (h->mv && (!im.min || !im.max))
+            return h->fail(FG_EINVAL, "%s: a multi-value operator's image needs the min and max columns", fn);
+        N += im.n;
+        if (N >= ((int64_t)1 << 32)) return h->fail(FG_EINVAL, "%s: the images hold 2^32 rows or more", fn);
+    }
+    const bool was_empty = h->tables.empty();   // (restored into a new handle: its tables equal the image)
+    h->cnt_bound = JMAX;
+    h->keys32 = false;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc0 = settle_pending(h)) return rc0;
+    int rc = flush(h);
+    if (rc) return rc;
+    fg_restore_info ri{};
+    ri.rows_in = N;
+    if (N > 0) {
+        rc = restore_rows(h, fn, images, n_images, location, filter, key_hash, N, &ri);
+        if (rc) return rc;
+    }
+    rc = restore_finish(h, timer_watermark, was_empty);
+    if (rc) return rc;
+    ri.state_regions = h->P;
+    if (info) *info = ri;
+    return FG_OK;
+}
+
+int fg_restore(fg_handle* h, const fg_state_rows* in, int64_t timer_watermark) {
+    if (!h || !in) return FG_EINVAL;
+    return restore_images(h, "fg_restore", in, 1, FG_HOST, false, 0, timer_watermark, nullptr);
 }
 
 int fg_restore_range(fg_handle* h, const fg_state_rows* images, int32_t n_images, int32_t location, int32_t key_hash,
@@ -4830,37 +4761,7 @@ int fg_restore_range(fg_handle* h, const fg_state_rows* images, int32_t n_images
     if (!(0 <= c.key_group_start && c.key_group_start <= c.key_group_end && c.key_group_end < c.max_parallelism))
         return h->fail(FG_EINVAL, "fg_restore_range: key-group range [%d, %d] is not within max parallelism %d",
                        c.key_group_start, c.key_group_end, c.max_parallelism);
-    int64_t N = 0;
-    for (int32_t g = 0; g < n_images; g++) {
-        const fg_state_rows& im = images[g];
-        if (im.n < 0) return h->fail(FG_EINVAL, "fg_restore_range: image %d has %lld rows", g, (long long)im.n);
-        if (im.n == 0) continue;
-        if (!im.key || !im.slice_end || !im.cnt_star || !im.cnt_val || !im.sum)
-            return h->fail(FG_EINVAL, "fg_restore_range: image %d lacks a column", g);
-        if (h->mv && (!im.min || !im.max))
-            return h->fail(FG_EINVAL, "a multi-value operator's image needs the min and max columns");
-        N += im.n;
-        if (N >= ((int64_t)1 << 32))
-            return h->fail(FG_EINVAL, "fg_restore_range: the images hold 2^32 rows or more");
-    }
-    const bool was_empty = h->tables.empty();
-    h->cnt_bound = JMAX;
-    h->keys32 = false;
-    HIPCHK(h, hipSetDevice(h->device));
-    if (int rc0 = settle_pending(h)) return rc0;
-    int rc = flush(h);
-    if (rc) return rc;
-    fg_restore_info ri{};
-    ri.rows_in = N;
-    if (N > 0) {
-        rc = restore_range_rows(h, images, n_images, location, key_hash, N, &ri);
-        if (rc) return rc;
-    }
-    rc = restore_finish(h, timer_watermark, was_empty);
-    if (rc) return rc;
-    ri.state_regions = h->P;
-    if (info) *info = ri;
-    return FG_OK;
+    return restore_images(h, "fg_restore_range", images, n_images, location, true, key_hash, timer_watermark, info);
 }
 
 int fg_late_dropped(fg_handle* h, int64_t* out) {

@@ -556,9 +556,9 @@ hipError_t launch_partition_by_owner(const int64_t* key, const int64_t* ts, cons
                                      size_t scratch_words, hipStream_t s);
 size_t partition_scratch_words(int64_t n, int32_t parallelism);
 
-// ---- rescale restore (fg_restore_range): the rows of several checkpoint images filtered by the
-// handle's key-group range and grouped by (slice, state region) into the SoA accumulator batch
-// (StagedBatch.is_acc) the merge consumes ----
+// ---- restore (fg_restore, fg_restore_range): the rows of one or several checkpoint images,
+// filtered by the handle's key-group range (fg_restore_range) or all of them (fg_restore), grouped
+// by (slice, state region) into the SoA accumulator batch (StagedBatch.is_acc) the merge consumes ----
 //   k_rr_dict     distinct slice ends of all rows into a small device table (wave-level dedup,
 //                 one 64-bit CAS per distinct value of a wave)
 //   k_rr_count    kept rows per (slice, top 13 bits of the key mix): the region sizing histogram
@@ -593,8 +593,8 @@ struct RrParams {
     int32_t n_images;
     int32_t grid;
     int64_t n;                 // rows of all images (< 2^32)
-    int32_t key_hash, max_p;   // key_group_of's arguments
-    int32_t kg_lo, kg_hi;      // kept: kg_lo <= key group <= kg_hi
+    int32_t key_hash, max_p;   // key_group_of's arguments; max_p == 0: no filter, every row is kept
+    int32_t kg_lo, kg_hi;      // kept: kg_lo <= key group <= kg_hi (not read without a filter)
     unsigned long long* dict;  // [kRrDictSlots] slice ends (kRrDictEmpty: free)
     uint32_t* dict_n;          // [0] distinct values in dict, [1] some row holds kRrDictEmpty itself
     const int64_t* slices;     // [n_slices] the distinct slice ends, ascending

@@ -3074,7 +3074,7 @@ hipError_t launch_partition_by_owner(const int64_t* key, const int64_t* ts, cons
 }
 
 // ----------------------------------------------------------------------------------------
-// rescale restore (fg_kernels.h): key-group filter, slice dictionary, (slice, region) grouping
+// restore (fg_kernels.h): key-group filter, slice dictionary, (slice, region) grouping
 // ----------------------------------------------------------------------------------------
 // the rows [beg, end) of the concatenated images, a workgroup's threads striding each image's part
 template <class F>
@@ -3087,6 +3087,7 @@ __device__ __forceinline__ void rr_rows(const RrParams& p, int64_t beg, int64_t 
     }
 }
 __device__ __forceinline__ bool rr_keep(const RrParams& p, int64_t key) {
+    if (p.max_p == 0) return true;   // no filter (kernel-uniform)
     const int32_t kg = key_group_of(key, p.key_hash, p.max_p);
     return kg >= p.kg_lo && kg <= p.kg_hi;
 }

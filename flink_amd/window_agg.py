@@ -525,10 +525,10 @@ class WindowAggOperator:
 
     def restore_state(self, image, timer_watermark: int):
         names = ("key", "slice_end", "cnt_star", "cnt_val", "sum") + (("min", "max") if "min" in image else ())
-        cols = {k: np.ascontiguousarray(image[k], dtype=np.int64) for k in names}
+        cols = {k: np.ascontiguousarray(image[k], dtype=np.int64) for k in names if image[k] is not None}
         s = L.FgStateRows()
         s.n = len(cols["key"])
-        for k in names:
+        for k in cols:   # (a missing column stays NULL: fg_restore refuses the image)
             setattr(s, k, cols[k].ctypes.data)
         L.check(self._lib.fg_restore(self._h, C.byref(s), int(timer_watermark)), self._h)
 

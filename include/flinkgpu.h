@@ -281,7 +281,9 @@ typedef struct fg_stats {
 } fg_stats;
 
 /* Per-kernel accounting (filled when FG_FLAG_KERNEL_TIMING is set): launches, summed
- * HIP-event duration on the handle's stream, records consumed and rows emitted. */
+ * HIP-event duration on the handle's stream, records consumed and rows emitted. A restore
+ * (fg_restore as well as fg_restore_range) records the classes restore_filter (slice dictionary,
+ * row counts), restore_scatter (grouping) and restore (the merges). */
 typedef struct fg_kernel_stat {
     char name[32];
     int64_t launches;
@@ -398,20 +400,31 @@ int  fg_snapshot_key_groups(fg_handle* h, fg_image_key_groups* out);
  * fg_last_error(NULL)) if it does not pass: a miscompiled build fails loudly instead of firing wrong
  * rows. */
 int  fg_selftest(int32_t device_id, char* msg, int32_t cap);
+/* Restore (initializeState): the rows of one host image (an fg_snapshot_state image, or the
+ * `window-aggs` entries a shim read from the keyed state backend) merged into the handle's state,
+ * and the handle left as open() + initializeState() leave the operator: progress at
+ * Long.MIN_VALUE, the timer watermark as DESIGN.md section 3 tells. Every row is kept --
+ * fg_config's key-group range and max parallelism are not read. fg_restore and fg_restore_range
+ * are two entry points of one pipeline: the image is uploaded whole, the grouping by slice and
+ * state region and the scatter run as kernels on the handle's stream, then one merge per slice; the
+ * host never reads a row. What fg_restore_range says below about row order and duplicates, the
+ * limits (at most 4096 distinct slice ends and fewer than 2^32 rows per call, else FG_EINVAL), the
+ * empty image (n == 0) and the device memory during the call holds here too.
+ *  - FG_EINVAL, before any device work: n < 0; n > 0 and a NULL key, slice_end, cnt_star, cnt_val or
+ *    sum; a NULL min or max for an operator with several value accumulators. The handle stays usable. */
 int  fg_restore(fg_handle* h, const fg_state_rows* in, int64_t timer_watermark);
 /* Rescale restore (ABI 16, added): fg_restore of the concatenation of images[0 .. n_images),
  * restricted to the rows whose key group lies in the handle's range,
  *   fg_config.key_group_start <= key_group(key, key_hash, fg_config.max_parallelism) <= key_group_end
  * (KeyGroupRangeAssignment; a restart at another parallelism hands every new subtask the images of
- * all old subtasks). The state after the call is what fg_restore leaves for that filtered image.
- * The filter, the grouping by slice and state region and the scatter run as kernels on the
- * handle's stream; the host never reads a row.
+ * all old subtasks). The state after the call is what fg_restore leaves for that filtered image:
+ * the filter is one more test in the kernels fg_restore runs.
  *  - timer_watermark: the minimum over the images' timer watermarks.
  *  - location FG_HOST: pageable or pinned columns, copied up on the handle's stream and read when the
  *    call returns. FG_DEVICE: device columns read in place on the handle's stream (the ordering rule
  *    of fg_location applies); they must not change during the call.
  *  - Rows may come in any order and a slice may occur in several images; duplicate (key, slice)
- *    rows merge as fg_restore merges them. With three or more DOUBLE duplicates of one (key, slice)
+ *    rows merge (counts and sums added, MIN of MIN, MAX of MAX). With three or more DOUBLE duplicates of one (key, slice)
  *    the summation order is unspecified. Rows listed slice by slice (as fg_snapshot_state writes
  *    them) are the fast case: the grouping walks a run of rows once per distinct slice end in it.
  *  - At most 4096 distinct slice ends among the rows of all images (foreign rows included) and fewer

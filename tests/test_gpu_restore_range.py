@@ -1,10 +1,13 @@
-"""Rescale restore on the GPU (fg_restore_range / WindowAggOperator.restore_state_range).
+"""Restore on the GPU (fg_restore / restore_state and fg_restore_range / restore_state_range: one
+pipeline behind two entry points).
 
-A. Equivalence with the existing path: for a key-group range R, restore_state_range(images) must
-   leave bit for bit the state that restore_state(host_filter(concat(images), R)) leaves, the
-   filter taken from the ORACLE's key groups (never from the code under test). Images hold each
-   (key, slice) once, so DOUBLE sums have no summation order to differ in: every column is compared
-   bit-exactly.
+A. For a key-group range R, restore_state_range(images) must leave bit for bit the state that
+   restore_state(host_filter(concat(images), R)) leaves, the filter taken from the ORACLE's key
+   groups (never from the code under test). Both entry points run the same kernels, so the state
+   of either handle is also compared with the expected image built in numpy alone
+   (assert_state_is). Images hold each (key, slice) once, so DOUBLE sums have no summation order
+   to differ in: every column is compared bit-exactly.
+A2. Plain restore_state, unfiltered, against the numpy image.
 B. Rescale against the oracle: P subtasks snapshot mid-stream, P' new subtasks restore their
    key-group ranges out of all P images, and the fired rows keep matching the single oracle
    operator (DOUBLE sums within test_gpu_parity's 1e-9 relative bar, everything else exact)."""
@@ -90,6 +93,41 @@ def assert_same_state(a, b, ctx=""):
         assert np.array_equal(ia[c].view(np.int64), ib[c].view(np.int64)), f"{ctx}: column {c} differs"
 
 
+def by_slice_and_key(img):
+    order = np.lexsort((img["key"], img["slice_end"]))
+    return {c: np.asarray(v)[order] for c, v in img.items()}
+
+
+def assert_state_is(op, expected_image, ctx=""):
+    """the operator's state against an image built in numpy alone (no engine code on this side):
+    every column of the snapshot, sorted by (slice_end, key) and viewed as int64. DOUBLE sums are
+    compared after x + 0.0, which maps -0.0 to +0.0 and changes nothing else."""
+    from flink_amd import _lib as L
+    got, exp = snap(op)[0], by_slice_and_key(expected_image)
+    assert set(got) == set(exp), f"{ctx}: columns {sorted(got)} vs {sorted(exp)} expected"
+    for c in got:
+        g, e = got[c].view(np.int64), exp[c].view(np.int64)
+        assert len(g) == len(e), f"{ctx}: {len(g)} rows vs {len(e)} expected"
+        if c == "sum" and op.val_type == L.VAL_F64:
+            g, e = ((x.view(np.float64) + 0.0).view(np.int64) for x in (g, e))
+        assert np.array_equal(g, e), f"{ctx}: column {c} differs from the expected image"
+
+
+def merged(img):
+    """numpy merge of the rows of an i64 image that share (key, slice): counts and sums added,
+    min of min, max of max"""
+    s = by_slice_and_key(img)
+    first = np.ones(len(s["key"]), dtype=bool)
+    first[1:] = (s["key"][1:] != s["key"][:-1]) | (s["slice_end"][1:] != s["slice_end"][:-1])
+    at = np.flatnonzero(first)
+    out = dict(key=s["key"][at], slice_end=s["slice_end"][at])
+    for c in ("cnt_star", "cnt_val", "sum"):
+        out[c] = np.add.reduceat(s[c], at)
+    if "min" in s:
+        out["min"], out["max"] = np.minimum.reduceat(s["min"], at), np.maximum.reduceat(s["max"], at)
+    return out
+
+
 def check_range_restore(O, spec, images, rng, twm, to_device=False, kg_of=None, key_hash=None, expected_keys=1 << 12,
                         maxp=MAXP, ctx=""):
     """path A (host filter + restore_state) against path B (restore_state_range) on fresh handles"""
@@ -110,6 +148,8 @@ def check_range_restore(O, spec, images, rng, twm, to_device=False, kg_of=None, 
         assert info["slices"] == len(np.unique(cat["slice_end"][keep])), (ctx, info)
         assert info["state_regions"] == b.stats()["state_regions"] == a.stats()["state_regions"], (ctx, info)
         assert_same_state(a, b, ctx)
+        assert_state_is(a, filt, ctx + " (restore_state)")
+        assert_state_is(b, filt, ctx + " (restore_state_range)")
         return info, b.stats()
     finally:
         a.close()
@@ -122,8 +162,9 @@ def synth(keys, slice_end=1_600_000_001_000, mv=False):
     i = np.arange(n, dtype=np.int64)
     img = dict(key=np.asarray(keys, dtype=np.int64), slice_end=np.full(n, slice_end, dtype=np.int64), cnt_star=i % 5 + 1,
                cnt_val=i % 5 + 1 - (i % 3 == 0), sum=(i * 0.5 + 1.0).view(np.int64))
-    if mv:
-        img["min"], img["max"] = i - 7, i + 7
+    if mv:   # (a row without a value holds the accumulators' identities, as a snapshot writes them)
+        none = img["cnt_val"] == 0
+        img["min"], img["max"] = np.where(none, JMAX, i - 7), np.where(none, -JMAX - 1, i + 7)
     return img
 
 
@@ -184,6 +225,12 @@ def test_device_images_equal_host_images(oracle_mod, name):
     check_range_restore(oracle_mod, OPS[name], split_parts(img), (0, 63), twm, to_device=True, ctx=name + " parts")
 
 
+# state_regions that the host implementation of restore_state left (the parent of the commit that
+# made it the unfiltered case of the GPU pipeline), measured there on an MI355X
+REGIONS_200K = {4096: 1024, 1000: 64}
+REGIONS_ONE_REGION = 8192
+
+
 @pytest.mark.parametrize("expected_keys", [4096, 1000])
 def test_restore_grows_the_regions(oracle_mod, expected_keys):
     """A one-slice image of 200,000 keys into a handle sized for far fewer. A handle opened for
@@ -197,14 +244,16 @@ def test_restore_grows_the_regions(oracle_mod, expected_keys):
     info, stats = check_range_restore(oracle_mod, spec, [synth(np.arange(200_000))], (0, 63), 1_600_000_000_000,
                                       expected_keys=expected_keys, ctx="200k keys")
     assert info["rows_kept"] > 90_000
+    assert stats["state_regions"] == REGIONS_200K[expected_keys], (info, before)
     if expected_keys < 4096:
         assert before == 1 and stats["state_regions"] > before, (info, before)
 
 
 def test_restore_of_keys_in_one_region(oracle_mod):
     """3000 of a region's 3584 entries at every split: sizing stops at the finest split and succeeds"""
-    check_range_restore(oracle_mod, OPS["tumble_f64"], [synth(keys_in_one_region(3000))], (0, 127), 1_600_000_000_000,
-                        ctx="one region")
+    _, stats = check_range_restore(oracle_mod, OPS["tumble_f64"], [synth(keys_in_one_region(3000))], (0, 127),
+                                   1_600_000_000_000, ctx="one region")
+    assert stats["state_regions"] == REGIONS_ONE_REGION
 
 
 def test_slice_end_equal_to_the_dictionary_marker(oracle_mod):
@@ -232,6 +281,9 @@ def test_restore_into_a_live_handle(oracle_mod):
             a.restore_state(host_filter(O, part, rng)[0], twm)
             b.restore_state_range([part], twm)
         assert_same_state(a, b, "live handle")
+        union = host_filter(O, img, rng)[0]
+        assert_state_is(a, union, "live handle (restore_state)")
+        assert_state_is(b, union, "live handle (restore_state_range)")
     finally:
         a.close()
         b.close()
@@ -285,6 +337,8 @@ def test_errors_leave_the_handle_usable(oracle_mod):
             a.restore_state(host_filter(O, valid, rng)[0], twm)
             b.restore_state_range([valid], twm)
             assert_same_state(a, b, f"after error {sorted(kw)} {len(bad['key'])}")
+            assert_state_is(a, host_filter(O, valid, rng)[0], "restore_state after an error")
+            assert_state_is(b, host_filter(O, valid, rng)[0], "restore_state_range after an error")
         finally:
             a.close()
             b.close()
@@ -299,9 +353,99 @@ def test_errors_leave_the_handle_usable(oracle_mod):
         a.restore_state(good, twm)
         b.restore_state(good, twm)
         assert_same_state(a, b, "after the range error")
+        assert_state_is(a, good, "restore_state beside the range error")
+        assert_state_is(b, good, "restore_state after the range error")
     finally:
         a.close()
         b.close()
+
+
+# ---- A2. plain restore_state against the numpy image -------------------------------------------------
+
+TWM = 1_600_000_000_000
+
+
+def check_plain_restore(spec, image, expected=None, twm=TWM, ctx="", **mk_kw):
+    op = mk(spec, **mk_kw)
+    try:
+        op.restore_state(image, twm)
+        assert_state_is(op, image if expected is None else expected, ctx)
+        return op.stats()
+    finally:
+        op.close()
+
+
+@pytest.mark.parametrize("n", [0, 1, 63, 64, 65, 257])
+def test_plain_restore_at_wave_and_workgroup_edges(n):
+    """every row is kept whatever the handle's key groups are: none configured, and one group"""
+    check_plain_restore(OPS["tumble_f64"], synth(np.arange(n)), ctx=f"n={n}, no max parallelism", rng=(0, 0), maxp=0)
+    check_plain_restore(OPS["tumble_f64"], synth(np.arange(n)), ctx=f"n={n}, range (5, 5)", rng=(5, 5))
+
+
+def test_plain_restore_of_the_dictionary_marker_slice():
+    spec = dict(OPS["tumble_f64"], offset=999)
+    image = concat([synth(np.arange(300), slice_end=-1), synth(np.arange(300, 500), slice_end=999)])
+    check_plain_restore(spec, image, twm=-5000, ctx="slice ends -1 and 999")
+
+
+def test_plain_restore_of_keys_in_one_region():
+    stats = check_plain_restore(OPS["tumble_f64"], synth(keys_in_one_region(3000)), ctx="one region")
+    assert stats["state_regions"] == REGIONS_ONE_REGION
+
+
+def test_plain_restore_multi_value():
+    check_plain_restore(OPS["multi_value_i64"], synth(np.arange(500), mv=True), ctx="multi-value")
+
+
+def test_plain_restore_merges_duplicate_rows():
+    """100 (key, slice) pairs occur three times each, shuffled across the image: the state is their
+    numpy merge (i64, so that the order of the additions cannot matter)"""
+    base = synth(np.arange(400), mv=True)
+    again = take(base, slice(150, 250))
+    image = concat([base, again, again])
+    image = take(image, np.random.default_rng(11).permutation(len(image["key"])))
+    exp = merged(image)
+    assert len(exp["key"]) == 400 and len(image["key"]) == 600
+    assert np.array_equal(exp["cnt_star"][150:250], 3 * base["cnt_star"][150:250])
+    check_plain_restore(OPS["multi_value_i64"], image, expected=exp, ctx="duplicates")
+
+
+def many_slice_ends(n_ends):
+    many = synth(np.arange(n_ends))
+    many["slice_end"] = 1_600_000_001_000 + 1000 * np.arange(n_ends, dtype=np.int64)
+    return many
+
+
+def test_plain_restore_slice_end_limit():
+    """every distinct slice end becomes a resident table: handles opened for 1,000 keys keep each at
+    one region"""
+    from flink_amd import _lib as L
+    check_plain_restore(OPS["tumble_f64"], many_slice_ends(4096), ctx="4096 slice ends", expected_keys=1000)
+    op = mk(OPS["tumble_f64"], expected_keys=1000)
+    try:
+        with pytest.raises(L.WindowSpecError, match="fg_restore:"):
+            op.restore_state(many_slice_ends(4097), TWM)
+        good = synth(np.arange(500))
+        op.restore_state(good, TWM)
+        assert_state_is(op, good, "after 4097 slice ends")
+    finally:
+        op.close()
+
+
+@pytest.mark.parametrize("name,bad", [("tumble_f64", dict(synth(np.arange(500)), sum=None)),   # NULL sum column
+                                      ("multi_value_i64", synth(np.arange(500)))],             # no min / max
+                         ids=["null_sum", "no_min_max"])
+def test_plain_restore_errors_leave_the_handle_usable(name, bad):
+    from flink_amd import _lib as L
+    op = mk(OPS[name])
+    try:
+        with pytest.raises(L.WindowSpecError):
+            op.restore_state(bad, TWM)
+        good = synth(np.arange(500), mv="aggs" in OPS[name])
+        op.restore_state(good, TWM)
+        assert_state_is(op, good, f"after {name} error")
+    finally:
+        op.close()
 
 
 # ---- B. rescale against the oracle -----------------------------------------------------------------
@@ -394,6 +538,8 @@ def test_restore_union_equals_union_image_for(oracle_mod):
         info = two_phase.restore_union(b, images)
         assert info["rows_kept"] == len(filt["key"])
         assert_same_state(a, b, "restore_union")
+        assert_state_is(a, filt, "union_image_for + restore_state")
+        assert_state_is(b, filt, "restore_union")
     finally:
         a.close()
         b.close()
