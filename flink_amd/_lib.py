@@ -128,6 +128,7 @@ EXPORTS = (
     "fg_collect_fired", "fg_collect_fired_to", "fg_flush", "fg_flush_partials", "fg_snapshot_state",
     "fg_snapshot_state_async", "fg_snapshot_state_wait", "fg_snapshot_slices", "fg_selftest", "fg_restore", "fg_restore_range", "fg_late_dropped", "fg_get_stats", "fg_synchronize", "fg_reset", "fg_kernel_stats", "fg_set_kernel_timing",
     "fg_set_snapshot_grouping", "fg_snapshot_key_groups",
+    "fg_snapshot_plan", "fg_snapshot_state_select_async", "fg_snapshot_state_select",
     "fg_stream",
     "fg_last_error", "fg_close", "fg_key_groups", "fg_partition_by_owner", "fg_partition_columns_by_owner",
     "fg_abi_version", "fg_key_dict_open", "fg_key_dict_intern", "fg_key_dict_intern_async",
@@ -243,6 +244,11 @@ def load():
     L.fg_snapshot_slices.argtypes = [P, C.POINTER(FgImageSlices)]
     L.fg_set_snapshot_grouping.argtypes = [P, C.c_int32]
     L.fg_snapshot_key_groups.argtypes = [P, C.POINTER(FgImageKeyGroups)]
+    L.fg_snapshot_plan.argtypes = [P, C.POINTER(FgImageSlices), C.POINTER(C.c_int64)]
+    L.fg_snapshot_state_select_async.argtypes = [P, P, C.c_int64]
+    L.fg_snapshot_state_select.argtypes = [P, P, C.c_int64, C.POINTER(FgStateRows), C.POINTER(C.c_int64)]
+    for fn in ("fg_snapshot_plan", "fg_snapshot_state_select_async", "fg_snapshot_state_select"):
+        getattr(L, fn).restype = C.c_int
     L.fg_selftest.argtypes = [C.c_int32, C.c_char_p, C.c_int32]
     L.fg_selftest.restype = C.c_int
     L.fg_comm_bytes_sent.argtypes = [P]

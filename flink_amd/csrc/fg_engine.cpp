@@ -175,12 +175,12 @@ constexpr int64_t kHeavyChunk = 1 << 16;
 
 enum KClass { K_COUNT = 0, K_SCAN, K_SCATTER, K_PART1, K_PART2, K_FLUSH, K_FLUSH_FIRE, K_FIRE, K_EXPORT, K_RESTORE,
               K_HEAVY, K_TILE1, K_TILE_FIRE, K_TILE_MAT, K_TILE_FLUSH, K_TILE_SPLIT, K_RR_FILTER, K_RR_SCATTER,
-              K_EXPORT_GROUP, K_NCLASS };
+              K_EXPORT_GROUP, K_EXPORT_SELECT, K_NCLASS };
 const char* const kClassName[K_NCLASS] = {"ingest_count", "ingest_scan",      "ingest_scatter", "ingest_part1",
                                            "ingest_part2", "merge_flush",      "merge_flush_fire", "merge_fire",
                                            "export",       "restore",          "merge_heavy",      "tile_part1",
                                            "tile_fire",    "tile_materialize", "tile_flush",       "tile_split_fire",
-                                           "restore_filter", "restore_scatter", "export_group"};
+                                           "restore_filter", "restore_scatter", "export_group",   "export_select"};
 struct KStat {
     int64_t launches = 0;
     double ms = 0;
@@ -324,6 +324,15 @@ struct fg_handle {
     DevBuf g_key, g_cs, g_cv, g_sum, g_v1, g_v2, kg_first, kg_cnt, kg_off, kg_tmp;
     HostBuf hs_kg_first, hs_kg_off;
     std::vector<int64_t> img_kg_first;
+    // selective images (fg_snapshot_plan / fg_snapshot_state_select_async): the resident slices as
+    // the last plan listed them (its region counts stay in hs_counts) -- valid until a call that
+    // may change the state, consumed by a select; the select's table descriptors
+    bool plan_valid = false;
+    int64_t plan_wm = 0;
+    std::vector<int64_t> plan_se, plan_first, plan_rows;
+    std::vector<uint8_t> plan_changed;
+    DevBuf sel_tab;
+    HostBuf hs_sel_tab;
     DevBuf hb_key[2], hb_ts[2], hb_val[2], hb_null[2];
     DevBuf hb_narrow[2];   // FG_HOST narrow columns (fg_batch.format) before widening
     hipEvent_t ev_copied[2] = {nullptr, nullptr}, ev_free[2] = {nullptr, nullptr};
@@ -3638,6 +3647,7 @@ int fg_open(const fg_config* cfg, fg_handle** out) {
 
 int fg_add_batch(fg_handle* h, const fg_batch* b) {
     if (!h || !b) return FG_EINVAL;
+    h->plan_valid = false;
     if (b->n <= 0) return FG_OK;
     if (b->n > (int64_t)0x7fffffff) return h->fail(FG_EINVAL, "batch larger than 2^31-1 records");
     if (!b->key || !b->rowtime) return h->fail(FG_EINVAL, "batch key/rowtime columns are required");
@@ -3806,6 +3816,7 @@ int fg_add_batch(fg_handle* h, const fg_batch* b) {
 
 int fg_add_rows(fg_handle* h, const fg_row_batch* b) {
     if (!h || !b) return FG_EINVAL;
+    h->plan_valid = false;
     if (b->n <= 0) return FG_OK;
     if (b->n > (int64_t)0x7fffffff) return h->fail(FG_EINVAL, "batch larger than 2^31-1 rows");
     if (!b->rows) return h->fail(FG_EINVAL, "rows pointer is required");
@@ -3880,6 +3891,7 @@ static int add_partials(fg_handle* h, const fg_partials* b) {
     if (h) {
         h->cnt_bound = JMAX;
         h->keys32 = false;
+        h->plan_valid = false;
     }
     if (!h || !b) return FG_EINVAL;
     if (b->n <= 0) return FG_OK;
@@ -3946,6 +3958,7 @@ static int add_partials(fg_handle* h, const fg_partials* b) {
 
 int fg_flush(fg_handle* h) {
     if (!h) return FG_EINVAL;
+    h->plan_valid = false;
     HIPCHK(h, hipSetDevice(h->device));
     if (int rc0 = settle_pending(h)) return rc0;
     return flush(h);
@@ -4087,6 +4100,7 @@ static void quiet_progress(fg_handle* h, int64_t wm) {   // advance()'s bookkeep
 
 int fg_advance_progress_async(fg_handle* h, int64_t wm) {
     if (!h) return FG_EINVAL;
+    h->plan_valid = false;
     HIPCHK(h, hipSetDevice(h->device));
     if (quiet_advance(h, wm)) {
         quiet_progress(h, wm);
@@ -4110,6 +4124,7 @@ int fg_advance_progress_async(fg_handle* h, int64_t wm) {
 
 int fg_advance_progress_async_n(fg_handle* h, const int64_t* wms, int64_t n) {
     if (!h || n < 0 || (n > 0 && !wms)) return FG_EINVAL;
+    h->plan_valid = false;
     for (int64_t i = 0; i < n; i++)
         if (int rc = fg_advance_progress_async(h, wms[i])) return rc;
     return FG_OK;
@@ -4130,6 +4145,7 @@ static void device_rows(fg_handle* h, int32_t out_location, fg_rows* fired) {
 
 int fg_collect_fired_to(fg_handle* h, int32_t out_location, fg_rows* fired) {
     if (!h || !fired || (out_location != FG_HOST && out_location != FG_DEVICE)) return FG_EINVAL;
+    h->plan_valid = false;
     HIPCHK(h, hipSetDevice(h->device));
     if (int rc = complete_fire(h)) return rc;
     if (!h->async_open) h->out_n = 0;   // (every async advance since the last collect fired nothing)
@@ -4149,6 +4165,7 @@ int fg_collect_fired(fg_handle* h, fg_rows* fired) { return fg_collect_fired_to(
 
 int fg_flush_partials(fg_handle* h, int32_t out_location, fg_rows* fired) {
     if (!h || !fired || (out_location != FG_HOST && out_location != FG_DEVICE)) return FG_EINVAL;
+    h->plan_valid = false;
     if (!h->local) return h->fail(FG_ESTATE, "fg_flush_partials on an operator without FG_FLAG_LOCAL_PARTIALS");
     HIPCHK(h, hipSetDevice(h->device));
     h->local_emit_all = true;
@@ -4168,6 +4185,7 @@ int fg_flush_partials(fg_handle* h, int32_t out_location, fg_rows* fired) {
 
 int fg_advance_progress(fg_handle* h, int64_t wm, int32_t out_location, fg_rows* fired) {
     if (!h) return FG_EINVAL;
+    h->plan_valid = false;
     HIPCHK(h, hipSetDevice(h->device));
     int rc = advance_progress(h, wm);   // (uncollected async rows lead its rows: adv_base)
     if (rc) return rc;
@@ -4192,7 +4210,7 @@ int fg_advance_progress(fg_handle* h, int64_t wm, int32_t out_location, fg_rows*
 // reordered by key group inside every slice into the second column set (g_*) on the handle's
 // stream; kg_off: the row offset of every (slice, key group). The slice_end column keeps its
 // place (a row stays in its slice), and an aliased cnt_val column is not moved.
-static int snapshot_group(fg_handle* h, int64_t total) {
+static int snapshot_group(fg_handle* h, int64_t total, bool any_null) {
     const int64_t S = (int64_t)h->img_se.size(), maxp = h->cfg.max_parallelism;
     if (S * maxp > kKgMaxBins || total >= ((int64_t)1 << 32))
         return h->fail(FG_EINVAL, "grouped snapshot: more than 2^30 (slice, key group) pairs or 2^32 rows");
@@ -4207,8 +4225,6 @@ static int snapshot_group(fg_handle* h, int64_t total) {
     HIPCHK(h, h->kg_off.ensure(4 * (size_t)(bins + 1)));
     HIPCHK(h, h->kg_tmp.ensure(4 * scan_tmp_words(bins)));
     HIPCHK(h, h->hs_kg_off.ensure(4 * (size_t)(bins + 1)));
-    bool any_null = false;
-    for (auto& kv : h->tables) any_null = any_null || kv.second->has_null;
     const size_t b8 = 8 * (size_t)total;
     KgParams p{};
     p.key = h->s_key.as<int64_t>();
@@ -4246,10 +4262,10 @@ static int snapshot_group(fg_handle* h, int64_t total) {
     return FG_OK;
 }
 
-// snapshotState's synchronous part: the staged records flushed, every resident slice exported
-// into the device image columns (s_*, in stream order: the image is the state as of this call)
-// and their copy into the pinned host image (hs_*) queued on the snapshot stream
-static int snapshot_begin(fg_handle* h) {
+// The plan half of a snapshot: the staged records flushed, a pending restore re-fire finished
+// and the region counts of every resident slice read into hs_counts ([table][region], the
+// tables' ascending order); rows[t]: the entries of table t
+static int snapshot_counts(fg_handle* h, std::vector<int64_t>& rows) {
     if (int rc0 = settle_pending(h)) return rc0;
     int rc = flush(h);
     if (rc) return rc;
@@ -4259,7 +4275,6 @@ static int snapshot_begin(fg_handle* h) {
         rc = refire_finish(h);
         if (rc) return rc;
     }
-    // region counts of every resident slice
     const size_t nt = h->tables.size();
     HIPCHK(h, h->hs_counts.ensure(sizeof(uint32_t) * h->P * std::max<size_t>(nt, 1)));
     size_t ti = 0;
@@ -4270,79 +4285,44 @@ static int snapshot_begin(fg_handle* h) {
     }
     rc = sync(h);
     if (rc) return rc;
-    int64_t total = 0;
-    HIPCHK(h, h->hs_off.ensure(sizeof(uint64_t) * h->P * std::max<size_t>(nt, 1)));
-    for (size_t t = 0; t < nt; t++) {
-        for (int r = 0; r < h->P; r++) {
-            h->hs_off.as<uint64_t>()[t * h->P + r] = (uint64_t)total;
-            total += h->hs_counts.as<uint32_t>()[t * h->P + r];
-        }
-    }
-    // the image's slices: its rows are grouped by slice, in the tables' (ascending) order
-    h->img_ready = false;
-    h->img_se.clear();
-    h->img_first.clear();
-    h->img_rows.clear();
-    h->img_changed.clear();
-    {
-        size_t t = 0;
-        for (auto& kv : h->tables) {
-            const int64_t first = (int64_t)h->hs_off.as<uint64_t>()[t * h->P];
-            const int64_t next = t + 1 < nt ? (int64_t)h->hs_off.as<uint64_t>()[(t + 1) * h->P] : total;
-            h->img_se.push_back(kv.first);
-            h->img_first.push_back(first);
-            h->img_rows.push_back(next - first);
-            h->img_changed.push_back(kv.second->changed ? 1 : 0);
-            kv.second->changed = false;
-            t++;
-        }
-    }
+    rows.assign(nt, 0);
+    for (size_t t = 0; t < nt; t++)
+        for (int r = 0; r < h->P; r++) rows[t] += h->hs_counts.as<uint32_t>()[t * h->P + r];
+    return FG_OK;
+}
+
+// The device image columns (s_*) and the pinned host image (hs_*) sized for `total` rows
+static int snapshot_columns(fg_handle* h, int64_t total) {
     const size_t b8 = 8 * (size_t)std::max<int64_t>(total, 1);
     HIPCHK(h, h->s_key.ensure(b8));
     HIPCHK(h, h->s_slice.ensure(b8));
     HIPCHK(h, h->s_cs.ensure(b8));
     HIPCHK(h, h->s_cv.ensure(b8));
     HIPCHK(h, h->s_sum.ensure(b8));
-    if (h->mv) {
-        HIPCHK(h, h->s_v1.ensure(b8));
-        HIPCHK(h, h->s_v2.ensure(b8));
-    }
-    HIPCHK(h, h->s_off.ensure(sizeof(uint64_t) * h->P * std::max<size_t>(nt, 1)));
-    HIPCHK(h, hipMemcpyAsync(h->s_off.p, h->hs_off.p, sizeof(uint64_t) * h->P * nt, hipMemcpyHostToDevice, h->stream));
-    ti = 0;
-    for (auto& kv : h->tables) {
-        ExportParams p{};
-        p.t = ref_of(kv.second.get());
-        p.region_off = h->s_off.as<uint64_t>() + ti * h->P;
-        p.slice_end = kv.first;
-        p.out_key = h->s_key.as<int64_t>();
-        p.out_slice = h->s_slice.as<int64_t>();
-        p.out_cnt_star = h->s_cs.as<int64_t>();
-        p.out_cnt_val = h->s_cv.as<int64_t>();
-        p.out_sum = h->s_sum.as<int64_t>();
-        p.mv = h->mv;
-        p.out_v1 = h->s_v1.as<int64_t>();
-        p.out_v2 = h->s_v2.as<int64_t>();
-        {
-            KTimer kt(h, K_EXPORT, 0);
-            HIPCHK(h, launch_export(p, h->P, h->stream));
-        }
-        ti++;
-    }
     HIPCHK(h, h->hs_key.ensure(b8));
     HIPCHK(h, h->hs_slice.ensure(b8));
     HIPCHK(h, h->hs_cs.ensure(b8));
     HIPCHK(h, h->hs_cv.ensure(b8));
     HIPCHK(h, h->hs_sum.ensure(b8));
     if (h->mv) {
+        HIPCHK(h, h->s_v1.ensure(b8));
+        HIPCHK(h, h->s_v2.ensure(b8));
         HIPCHK(h, h->hs_v1.ensure(b8));
         HIPCHK(h, h->hs_v2.ensure(b8));
     }
+    return FG_OK;
+}
+
+// The back half of a snapshot: the exported image (s_*, `total` rows in the slices of img_se /
+// img_first) grouped by key group if the grouping is on, and its copy into the pinned host image
+// (hs_*) queued on the snapshot stream. any_null: some exported table counts NULL values (else
+// the cnt_val column was not needed and is neither moved nor copied).
+static int snapshot_queue(fg_handle* h, int64_t total, bool any_null) {
     h->snap_grouped = h->snap_group >= 0;
     const int64_t *d_key = h->s_key.as<int64_t>(), *d_cs = h->s_cs.as<int64_t>(), *d_cv = h->s_cv.as<int64_t>(),
                   *d_sum = h->s_sum.as<int64_t>(), *d_v1 = h->s_v1.as<int64_t>(), *d_v2 = h->s_v2.as<int64_t>();
     if (h->snap_grouped) {
-        if (int rcg = snapshot_group(h, total)) {
+        if (int rcg = snapshot_group(h, total, any_null)) {
             h->snap_grouped = false;
             return rcg;
         }
@@ -4372,8 +4352,6 @@ static int snapshot_begin(fg_handle* h) {
         HIPCHK(h, hipMemcpyAsync(h->hs_cs.p, d_cs, 8 * total, kd, cs));
         // no table counts NULL values: COUNT(v) = COUNT(*) for every entry, and the image's
         // cnt_val column is its cnt_star column (a fifth less to copy while the job runs on)
-        bool any_null = false;
-        for (auto& kv : h->tables) any_null = any_null || kv.second->has_null;
         h->snap_cv_alias = !any_null;
         if (any_null) HIPCHK(h, hipMemcpyAsync(h->hs_cv.p, d_cv, 8 * total, kd, cs));
         HIPCHK(h, hipMemcpyAsync(h->hs_sum.p, d_sum, 8 * total, kd, cs));
@@ -4384,6 +4362,171 @@ static int snapshot_begin(fg_handle* h) {
     h->snap_total = total;
     h->snap_wm = h->timer_wm;
     return FG_OK;
+}
+
+// snapshotState's synchronous part: the staged records flushed, every resident slice exported
+// into the device image columns (s_*, in stream order: the image is the state as of this call)
+// and their copy into the pinned host image (hs_*) queued on the snapshot stream
+static int snapshot_begin(fg_handle* h) {
+    std::vector<int64_t> rows;
+    int rc = snapshot_counts(h, rows);
+    if (rc) return rc;
+    const size_t nt = h->tables.size();
+    int64_t total = 0;
+    HIPCHK(h, h->hs_off.ensure(sizeof(uint64_t) * h->P * std::max<size_t>(nt, 1)));
+    for (size_t t = 0; t < nt; t++) {
+        for (int r = 0; r < h->P; r++) {
+            h->hs_off.as<uint64_t>()[t * h->P + r] = (uint64_t)total;
+            total += h->hs_counts.as<uint32_t>()[t * h->P + r];
+        }
+    }
+    // the image's slices: its rows are grouped by slice, in the tables' (ascending) order
+    h->img_ready = false;
+    h->img_se.clear();
+    h->img_first.clear();
+    h->img_rows.clear();
+    h->img_changed.clear();
+    bool any_null = false;
+    {
+        size_t t = 0;
+        for (auto& kv : h->tables) {
+            h->img_se.push_back(kv.first);
+            h->img_first.push_back((int64_t)h->hs_off.as<uint64_t>()[t * h->P]);
+            h->img_rows.push_back(rows[t]);
+            h->img_changed.push_back(kv.second->changed ? 1 : 0);
+            kv.second->changed = false;
+            any_null = any_null || kv.second->has_null;
+            t++;
+        }
+    }
+    if (int rcc = snapshot_columns(h, total)) return rcc;
+    HIPCHK(h, h->s_off.ensure(sizeof(uint64_t) * h->P * std::max<size_t>(nt, 1)));
+    HIPCHK(h, hipMemcpyAsync(h->s_off.p, h->hs_off.p, sizeof(uint64_t) * h->P * nt, hipMemcpyHostToDevice, h->stream));
+    size_t ti = 0;
+    for (auto& kv : h->tables) {
+        ExportParams p{};
+        p.t = ref_of(kv.second.get());
+        p.region_off = h->s_off.as<uint64_t>() + ti * h->P;
+        p.slice_end = kv.first;
+        p.out_key = h->s_key.as<int64_t>();
+        p.out_slice = h->s_slice.as<int64_t>();
+        p.out_cnt_star = h->s_cs.as<int64_t>();
+        p.out_cnt_val = h->s_cv.as<int64_t>();
+        p.out_sum = h->s_sum.as<int64_t>();
+        p.mv = h->mv;
+        p.out_v1 = h->s_v1.as<int64_t>();
+        p.out_v2 = h->s_v2.as<int64_t>();
+        {
+            KTimer kt(h, K_EXPORT, 0);
+            HIPCHK(h, launch_export(p, h->P, h->stream));
+        }
+        ti++;
+    }
+    return snapshot_queue(h, total, any_null);
+}
+
+// fg_snapshot_plan: the resident slices and what a full image taken now would hold of them
+static int snapshot_plan(fg_handle* h) {
+    h->plan_valid = false;
+    std::vector<int64_t> rows;
+    if (int rc = snapshot_counts(h, rows)) return rc;
+    h->plan_se.clear();
+    h->plan_first.clear();
+    h->plan_changed.clear();
+    int64_t total = 0;
+    size_t t = 0;
+    for (auto& kv : h->tables) {
+        h->plan_se.push_back(kv.first);
+        h->plan_first.push_back(total);
+        h->plan_changed.push_back(kv.second->changed ? 1 : 0);
+        total += rows[t++];
+    }
+    h->plan_rows = std::move(rows);
+    h->plan_wm = h->timer_wm;
+    h->plan_valid = true;
+    return FG_OK;
+}
+
+// fg_snapshot_state_select_async: the planned slices with want[i] != 0 exported by one k_export_sel
+// launch into a compact image. The descriptors and the 64-bit region offsets come from the counts
+// the plan read (hs_counts): nothing is read back between this call and the launch.
+static int snapshot_select(fg_handle* h, const uint8_t* want, int64_t n) {
+    if (!h->plan_valid) return h->fail(FG_ESTATE, "fg_snapshot_state_select: no valid fg_snapshot_plan (a call since the plan may have changed the state)");
+    const size_t nt = h->plan_se.size();
+    if (n != (int64_t)nt)
+        return h->fail(FG_EINVAL, "fg_snapshot_state_select: n = %lld, the plan lists %lld slices", (long long)n, (long long)nt);
+    if (n > 0 && !want) return h->fail(FG_EINVAL, "fg_snapshot_state_select: want is NULL");
+    int64_t total = 0;
+    size_t nsel = 0;
+    for (size_t t = 0; t < nt; t++) {
+        if (!want[t]) continue;
+        nsel++;
+        total += h->plan_rows[t];
+        if (total >= ((int64_t)1 << 32)) return h->fail(FG_EINVAL, "fg_snapshot_state_select: 2^32 or more selected rows");
+    }
+    if (nsel > 65535) return h->fail(FG_EINVAL, "fg_snapshot_state_select: more than 65535 selected slices");
+    h->plan_valid = false;   // consumed
+    const size_t P = (size_t)h->P;
+    HIPCHK(h, h->hs_sel_tab.ensure(sizeof(ExportSelTable) * std::max<size_t>(nsel, 1)));
+    HIPCHK(h, h->hs_off.ensure(sizeof(uint64_t) * (P + 1) * std::max<size_t>(nsel, 1)));
+    h->img_ready = false;
+    h->img_se.clear();
+    h->img_first.clear();
+    h->img_rows.clear();
+    h->img_changed.clear();
+    bool any_null = false;
+    {
+        size_t t = 0, j = 0;
+        int64_t base = 0;
+        for (auto& kv : h->tables) {
+            if (want[t]) {
+                ExportSelTable& d = h->hs_sel_tab.as<ExportSelTable>()[j];
+                d.t = ref_of(kv.second.get());
+                d.slice_end = kv.first;
+                d.row_base = base;
+                uint64_t* off = h->hs_off.as<uint64_t>() + j * (P + 1);
+                uint64_t o = 0;
+                for (size_t r = 0; r < P; r++) {
+                    off[r] = o;
+                    o += h->hs_counts.as<uint32_t>()[t * P + r];
+                }
+                off[P] = o;
+                h->img_se.push_back(kv.first);
+                h->img_first.push_back(base);
+                h->img_rows.push_back(h->plan_rows[t]);
+                h->img_changed.push_back(h->plan_changed[t]);
+                kv.second->changed = false;
+                any_null = any_null || kv.second->has_null;
+                base += h->plan_rows[t];
+                j++;
+            }
+            t++;
+        }
+    }
+    if (int rcc = snapshot_columns(h, total)) return rcc;
+    if (nsel > 0) {
+        HIPCHK(h, h->sel_tab.ensure(sizeof(ExportSelTable) * nsel));
+        HIPCHK(h, h->s_off.ensure(sizeof(uint64_t) * (P + 1) * nsel));
+        HIPCHK(h, hipMemcpyAsync(h->sel_tab.p, h->hs_sel_tab.p, sizeof(ExportSelTable) * nsel, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->s_off.p, h->hs_off.p, sizeof(uint64_t) * (P + 1) * nsel, hipMemcpyHostToDevice, h->stream));
+        ExportSelParams p{};
+        p.tables = h->sel_tab.as<ExportSelTable>();
+        p.region_off = h->s_off.as<uint64_t>();
+        p.regions = h->P;
+        p.n_tables = (int32_t)nsel;
+        p.out_key = h->s_key.as<int64_t>();
+        p.out_slice = h->s_slice.as<int64_t>();
+        p.out_cnt_star = h->s_cs.as<int64_t>();
+        p.out_cnt_val = h->s_cv.as<int64_t>();
+        p.out_sum = h->s_sum.as<int64_t>();
+        p.out_v1 = h->s_v1.as<int64_t>();
+        p.out_v2 = h->s_v2.as<int64_t>();
+        p.mv = h->mv;
+        p.with_cv = any_null ? 1 : 0;
+        KTimer kt(h, K_EXPORT_SELECT, total);
+        HIPCHK(h, launch_export_sel(p, h->stream));
+    }
+    return snapshot_queue(h, total, any_null);
 }
 
 // snapshotState's asynchronous part: the host image once its copy has completed
@@ -4412,6 +4555,7 @@ static int snapshot_end(fg_handle* h, fg_state_rows* out, int64_t* timer_waterma
 
 int fg_set_snapshot_grouping(fg_handle* h, int32_t key_hash) {
     if (!h) return FG_EINVAL;
+    h->plan_valid = false;
     if (key_hash >= 0 && key_hash != FG_KEYHASH_BINARYROW_BIGINT && key_hash != FG_KEYHASH_JAVA_LONG &&
         key_hash != FG_KEYHASH_DICT_ID)
         return h->fail(FG_EINVAL, "fg_set_snapshot_grouping: unknown key_hash %d", key_hash);
@@ -4425,6 +4569,7 @@ int fg_set_snapshot_grouping(fg_handle* h, int32_t key_hash) {
 
 int fg_snapshot_key_groups(fg_handle* h, fg_image_key_groups* out) {
     if (!h || !out) return FG_EINVAL;
+    h->plan_valid = false;
     if (!h->img_ready) return h->fail(FG_ESTATE, "fg_snapshot_key_groups: no image returned since the last snapshot call");
     if (!h->snap_grouped) return h->fail(FG_ESTATE, "fg_snapshot_key_groups: the image was taken with grouping off");
     out->n_slices = (int64_t)h->img_se.size();
@@ -4435,6 +4580,7 @@ int fg_snapshot_key_groups(fg_handle* h, fg_image_key_groups* out) {
 
 int fg_snapshot_slices(fg_handle* h, fg_image_slices* out) {
     if (!h || !out) return FG_EINVAL;
+    h->plan_valid = false;
     if (!h->img_ready) return h->fail(FG_ESTATE, "fg_snapshot_slices: no image returned since the last snapshot call");
     out->n = (int64_t)h->img_se.size();
     out->slice_end = h->img_se.data();
@@ -4446,6 +4592,7 @@ int fg_snapshot_slices(fg_handle* h, fg_image_slices* out) {
 
 int fg_snapshot_state_async(fg_handle* h) {
     if (!h) return FG_EINVAL;
+    h->plan_valid = false;
     HIPCHK(h, hipSetDevice(h->device));
     if (h->snap_pending) return h->fail(FG_ESTATE, "an asynchronous snapshot is not collected yet (fg_snapshot_state_wait)");
     return snapshot_begin(h);
@@ -4453,15 +4600,44 @@ int fg_snapshot_state_async(fg_handle* h) {
 
 int fg_snapshot_state_wait(fg_handle* h, fg_state_rows* out, int64_t* timer_watermark) {
     if (!h || !out) return FG_EINVAL;
+    h->plan_valid = false;
     HIPCHK(h, hipSetDevice(h->device));
     return snapshot_end(h, out, timer_watermark);
 }
 
 int fg_snapshot_state(fg_handle* h, fg_state_rows* out, int64_t* timer_watermark) {
     if (!h || !out) return FG_EINVAL;
+    h->plan_valid = false;
     HIPCHK(h, hipSetDevice(h->device));
     if (h->snap_pending) return h->fail(FG_ESTATE, "an asynchronous snapshot is not collected yet (fg_snapshot_state_wait)");
     if (int rc = snapshot_begin(h)) return rc;
+    return snapshot_end(h, out, timer_watermark);
+}
+
+int fg_snapshot_plan(fg_handle* h, fg_image_slices* out, int64_t* timer_watermark) {
+    if (!h || !out) return FG_EINVAL;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (h->snap_pending) return h->fail(FG_ESTATE, "an asynchronous snapshot is not collected yet (fg_snapshot_state_wait)");
+    if (int rc = snapshot_plan(h)) return rc;
+    out->n = (int64_t)h->plan_se.size();
+    out->slice_end = h->plan_se.data();
+    out->first_row = h->plan_first.data();
+    out->rows = h->plan_rows.data();
+    out->changed = h->plan_changed.data();
+    if (timer_watermark) *timer_watermark = h->plan_wm;
+    return FG_OK;
+}
+
+int fg_snapshot_state_select_async(fg_handle* h, const uint8_t* want, int64_t n) {
+    if (!h) return FG_EINVAL;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (h->snap_pending) return h->fail(FG_ESTATE, "an asynchronous snapshot is not collected yet (fg_snapshot_state_wait)");
+    return snapshot_select(h, want, n);
+}
+
+int fg_snapshot_state_select(fg_handle* h, const uint8_t* want, int64_t n, fg_state_rows* out, int64_t* timer_watermark) {
+    if (!h || !out) return FG_EINVAL;
+    if (int rc = fg_snapshot_state_select_async(h, want, n)) return rc;
     return snapshot_end(h, out, timer_watermark);
 }
 
@@ -4745,12 +4921,14 @@ static int restore_images(fg_handle* h, const char* fn, const fg_state_rows* ima
 
 int fg_restore(fg_handle* h, const fg_state_rows* in, int64_t timer_watermark) {
     if (!h || !in) return FG_EINVAL;
+    h->plan_valid = false;
     return restore_images(h, "fg_restore", in, 1, FG_HOST, false, 0, timer_watermark, nullptr);
 }
 
 int fg_restore_range(fg_handle* h, const fg_state_rows* images, int32_t n_images, int32_t location, int32_t key_hash,
                      int64_t timer_watermark, fg_restore_info* info) {
     if (!h) return FG_EINVAL;
+    h->plan_valid = false;
     if (n_images < 0 || (n_images > 0 && !images))
         return h->fail(FG_EINVAL, "fg_restore_range: %d images", n_images);
     if (location != FG_HOST && location != FG_DEVICE)
@@ -4793,6 +4971,7 @@ int fg_synchronize(fg_handle* h) {
 
 int fg_reset(fg_handle* h) {
     if (!h) return FG_EINVAL;
+    h->plan_valid = false;
     HIPCHK(h, hipSetDevice(h->device));
     if (int rc0 = settle_pending(h)) return rc0;
     int rc = sync(h);

@@ -347,6 +347,31 @@ struct ExportParams {
     int32_t pad;
 };
 
+// Selective image (k_export_sel): one descriptor per selected table, ascending by slice; the rows
+// of (table t, region r) go to image rows row_base + [off[r], off[r + 1]), off = region_off +
+// t * (regions + 1): the exclusive prefix of the table's region counts, regions + 1 entries.
+struct ExportSelTable {
+    TableRef t;
+    int64_t slice_end;
+    int64_t row_base;            // the slice's first image row
+};
+struct ExportSelParams {
+    const ExportSelTable* tables;
+    const uint64_t* region_off;
+    int32_t regions;
+    int32_t n_tables;
+    int64_t* out_key;
+    int64_t* out_slice;
+    int64_t* out_cnt_star;
+    int64_t* out_cnt_val;        // written only with with_cv (some selected table counts NULL values)
+    int64_t* out_sum;
+    int64_t* out_v1;             // multi-value operator: value slots 1 and 2
+    int64_t* out_v2;
+    int32_t mv;
+    int32_t with_cv;
+};
+hipError_t launch_export_sel(const ExportSelParams& p, hipStream_t s);
+
 hipError_t launch_ingest_count(const IngestParams& p, hipStream_t s);
 // global phase: rowtime = slice_end - 1 - tz for partial rows; scatter of accumulator rows
 hipError_t launch_pseudo_rowtime(const int64_t* slice_end, int64_t n, int64_t tz, int64_t* out, hipStream_t s);

@@ -13,6 +13,8 @@
 //                                      and/or emits fired rows (fireWindow + mergeSlices,
 //                                      processors/SliceSharedWindowAggProcessor.java:64-118)
 //   k_export                           checkpoint image of the resident state
+//   k_export_sel                       selective checkpoint image: the tables of a descriptor array
+//                                      (the slices a caller selected) in one launch
 //   k_key_groups / k_owner_*           KeyGroupRangeAssignment routing for the key-group exchange
 //   k_rr_*                             rescale restore: checkpoint images filtered by key-group range
 //                                      and grouped by (slice, region) for the merge
@@ -2874,6 +2876,45 @@ __global__ __launch_bounds__(256) void k_export(ExportParams p) {
 
 hipError_t launch_export(const ExportParams& p, int32_t regions, hipStream_t s) {
     fg_launch(k_export, dim3(regions), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
+// selective image: the tables of one descriptor array in one launch, grid (region, selected table).
+// A workgroup walks its region as k_export does (consecutive lanes on consecutive entries of every
+// column); the layout flag and the counts are the table's own, the row offsets 64-bit. The entries
+// written are bounded by the offsets' span, so that a count the host did not plan for cannot write
+// past the image. WITH_CV = false: no selected table counts NULL values, the cnt_val column is the
+// cnt_star column and is not written.
+template <bool WITH_CV>
+__global__ __launch_bounds__(256) void k_export_sel(ExportSelParams p) {
+    const int r = blockIdx.x;
+    const ExportSelTable d = p.tables[blockIdx.y];
+    const uint64_t* ro = p.region_off + (size_t)blockIdx.y * (p.regions + 1) + r;
+    const uint64_t o = (uint64_t)d.row_base + ro[0];
+    const uint64_t span = ro[1] - ro[0];
+    uint32_t n = gbl(d.t.counts)[r];
+    if ((uint64_t)n > span) n = (uint32_t)span;
+    const int cap = table_cap(p.mv);
+    const auto base = gbl(d.t.base + (int64_t)r * table_cols(p.mv) * cap);
+    const bool nar = d.t.narrow != 0;
+    for (uint32_t i = threadIdx.x; i < n; i += 256) {
+        const int64_t cs = tab_cs(base, cap, i, nar);
+        p.out_key[o + i] = nar ? (int64_t)tab_key32(base, cap, i, nar) : key_of(base[i]);
+        p.out_slice[o + i] = d.slice_end;
+        p.out_cnt_star[o + i] = cs;
+        if constexpr (WITH_CV) p.out_cnt_val[o + i] = cs - tab_cn(base, cap, i, nar);
+        p.out_sum[o + i] = tab_v(base, cap, i, nar);
+        if (p.mv) {
+            p.out_v1[o + i] = base[4 * cap + i];
+            p.out_v2[o + i] = base[5 * cap + i];
+        }
+    }
+}
+
+hipError_t launch_export_sel(const ExportSelParams& p, hipStream_t s) {
+    if (p.regions < 1 || p.n_tables < 1 || p.n_tables > 65535) return hipErrorInvalidValue;
+    if (p.with_cv) fg_launch(k_export_sel<true>, dim3(p.regions, p.n_tables), dim3(256), 0, s, p);
+    else fg_launch(k_export_sel<false>, dim3(p.regions, p.n_tables), dim3(256), 0, s, p);
     return hipGetLastError();
 }
 

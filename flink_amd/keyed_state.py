@@ -25,6 +25,9 @@ must bring the backend up to date with the engine's image -- incrementally (`wri
   the progress (SliceSharedWindowAggProcessor.fireWindow's nextTriggerWindow): registered for the keys
   of changed namespaces, and for every such key when the next window end moved.
 
+`write_delta` is `write_image` from a selective image (fg_snapshot_plan -> `wanted_slices` ->
+fg_snapshot_state_select): the engine exports and copies only the slices whose namespaces are rewritten.
+
 `write_image_full` is round 5's rewrite (every entry cleared and put again, every timer deleted and
 registered), kept as the cross-check: both leave the backend in the same state.
 """
@@ -136,21 +139,38 @@ class WindowAggsState:
                 m[key] = acc if prev is None else merge_acc(prev, acc, self.f64)
         return out
 
-    def _fired_keys(self, image, slices, progress, wanted=None):
+    def _fired_keys(self, image, slices, progress, wanted=None, image_slices=None):
+        """the keys of the fired slices of `slices` (those whose namespace is in `wanted`, all if
+        None). `image_slices`: the slices `image` holds, if not all of `slices` (a selective image);
+        the keys of a fired slice the image lacks come from the backend's own entries of its
+        namespace (getKeys(state, namespace)): the slice is unchanged, so the backend holds them."""
+        held = slices if image_slices is None else image_slices
+        at = {se: (first, nrow) for se, first, nrow in zip(held["slice_end"].tolist(), held["first_row"].tolist(),
+                                                           held["rows"].tolist())}
         keys = set()
-        for se, first, nrow in zip(slices["slice_end"].tolist(), slices["first_row"].tolist(),
-                                   slices["rows"].tolist()):
+        scanned = set()
+        for se in slices["slice_end"].tolist():
             if not self.spec.is_fired(se, progress):
                 continue
-            if wanted is not None and self.spec.namespace(se, progress) not in wanted:
+            ns = self.spec.namespace(se, progress)
+            if wanted is not None and ns not in wanted:
                 continue
-            keys.update(int(k) for k in image["key"][first:first + nrow])
+            if se in at:
+                first, nrow = at[se]
+                keys.update(int(k) for k in image["key"][first:first + nrow])
+            elif ns not in scanned:
+                scanned.add(ns)
+                for kn in self.entries:
+                    if kn[1] == ns:
+                        self.ops["scan"] += 1
+                        keys.add(kn[0])
         return keys
 
-    def write_image(self, image, slices, progress: int) -> dict:
-        """writeKeyedState, incremental. `image`: the engine's snapshot columns; `slices`:
-        fg_snapshot_slices; `progress`: the image's timer watermark. Returns this call's op counts."""
-        before = dict(self.ops)
+    def _plan(self, slices, progress: int):
+        """(contrib, changed, reset) of an image's or a plan's slices: the slices of every namespace,
+        whether the namespace is rewritten, and the namespaces rebuilt because their slices are not
+        the ones they held at the last image (a CUMULATE slice that fired since moved into its
+        window's namespace, or left one)"""
         sp = self.spec
         contrib: dict[int, set] = {}
         changed: dict[int, bool] = {}
@@ -158,11 +178,41 @@ class WindowAggsState:
             ns = sp.namespace(se, progress)
             contrib.setdefault(ns, set()).add(se)
             changed[ns] = changed.get(ns, False) or bool(ch)
-        # a namespace whose slices are not the ones it held at the last image (a CUMULATE slice that
-        # fired since moved into its window's namespace, or left one) is rebuilt: cleared, then put
         reset = {ns for ns, c in contrib.items() if ns in self.contrib and self.contrib[ns] != c}
         for ns in reset:
             changed[ns] = True
+        return contrib, changed, reset
+
+    def wanted_slices(self, plan_slices, progress: int) -> np.ndarray:
+        """The mask of fg_snapshot_state_select for a plan (fg_snapshot_plan's slices, `progress`
+        its timer watermark): every slice whose namespace write_image would rewrite -- changed, or
+        rebuilt (all contributors of a CUMULATE namespace when one of them changed or fired)."""
+        _, changed, _ = self._plan(plan_slices, progress)
+        return np.array([1 if changed[self.spec.namespace(se, progress)] else 0
+                         for se in plan_slices["slice_end"].tolist()], dtype=np.uint8)
+
+    def write_image(self, image, slices, progress: int) -> dict:
+        """writeKeyedState, incremental. `image`: the engine's snapshot columns; `slices`:
+        fg_snapshot_slices; `progress`: the image's timer watermark. Returns this call's op counts."""
+        return self._write(image, slices, slices, progress)
+
+    def write_delta(self, image, image_slices, plan_slices, progress: int) -> dict:
+        """writeKeyedState from a selective image: `image` / `image_slices` are what
+        fg_snapshot_state_select returned for the mask wanted_slices(plan_slices, progress) (or a
+        superset of it). Leaves the backend exactly as write_image(full image, plan_slices, progress)
+        would, reading rows of the selective image only."""
+        return self._write(image, image_slices, plan_slices, progress)
+
+    def _write(self, image, image_slices, slices, progress: int) -> dict:
+        before = dict(self.ops)
+        sp = self.spec
+        contrib, changed, reset = self._plan(slices, progress)
+        dirty = {ns for ns, c in changed.items() if c}
+        if image_slices is not slices:
+            have = set(image_slices["slice_end"].tolist())
+            lack = [se for se in slices["slice_end"].tolist() if sp.namespace(se, progress) in dirty and se not in have]
+            if lack:
+                raise ValueError(f"write_delta: the image lacks slices {lack} of namespaces to rewrite")
         # namespaces gone since the previous image, and the ones rebuilt: cleared (their keys from
         # getKeys(state, namespace))
         for ns in sorted((self.namespaces - set(changed)) | reset):
@@ -170,8 +220,7 @@ class WindowAggsState:
                 self.ops["scan"] += 1
                 del self.entries[kn]
                 self.ops["clear"] += 1
-        dirty = {ns for ns, c in changed.items() if c}
-        for ns, m in self._namespace_images(image, slices, progress, wanted=dirty).items():
+        for ns, m in self._namespace_images(image, image_slices, progress, wanted=dirty).items():
             for key, acc in m.items():
                 self.entries[(key, ns)] = acc
                 self.ops["put"] += 1
@@ -180,7 +229,8 @@ class WindowAggsState:
         if not self.proctime:
             nxt = sp.next_end(progress)
             moved = nxt != self.last_next_end
-            for key in self._fired_keys(image, slices, progress, wanted=None if moved else dirty):
+            for key in self._fired_keys(image, slices, progress, wanted=None if moved else dirty,
+                                        image_slices=image_slices):
                 self._register(key, nxt)
             self.last_next_end = nxt
         self.namespaces = set(changed)

@@ -491,11 +491,46 @@ class WindowAggOperator:
             img["min"], img["max"] = col(s.min), col(s.max)
         return img, wm.value
 
+    def snapshot_plan(self):
+        """fg_snapshot_plan: (slices, timer watermark) -- every resident slice as snapshot_slices
+        lists the slices of an image (first_row: its place in a full snapshot_state image taken
+        now), without exporting or copying a row and without clearing a changed flag. The mask of
+        snapshot_state_select[_async] indexes these slices; any call that may change the state
+        invalidates the plan."""
+        s = L.FgImageSlices()
+        wm = C.c_int64()
+        L.check(self._lib.fg_snapshot_plan(self._h, C.byref(s), C.byref(wm)), self._h)
+        return self._slices(s), wm.value
+
+    @staticmethod
+    def _want(want):
+        w = np.zeros(0, dtype=np.uint8) if want is None else np.ascontiguousarray(np.asarray(want) != 0, dtype=np.uint8)
+        return w, (w.ctypes.data if len(w) else None)
+
+    def snapshot_state_select(self, want, copy: bool = True):
+        """fg_snapshot_state_select: the image (as snapshot_state returns it) of the planned slices
+        i with want[i] != 0 only, compact and grouped by slice; snapshot_slices then describes it."""
+        w, ptr = self._want(want)
+        s = L.FgStateRows()
+        wm = C.c_int64()
+        L.check(self._lib.fg_snapshot_state_select(self._h, ptr, len(w), C.byref(s), C.byref(wm)), self._h)
+        return self._image(s, wm, copy)
+
+    def snapshot_state_select_async(self, want):
+        """snapshot_state_select's synchronous part (one export launch, the copy queued);
+        snapshot_state_wait returns the image."""
+        w, ptr = self._want(want)
+        L.check(self._lib.fg_snapshot_state_select_async(self._h, ptr, len(w)), self._h)
+
     def snapshot_slices(self) -> dict:
         """fg_snapshot_slices: the slices of the image the last snapshot returned -- slice_end,
         first_row, rows (its rows in the image), changed (written since the image before)."""
         s = L.FgImageSlices()
         L.check(self._lib.fg_snapshot_slices(self._h, C.byref(s)), self._h)
+        return self._slices(s)
+
+    @staticmethod
+    def _slices(s) -> dict:
         n = int(s.n)
 
         def col(p, ct, dt):

@@ -394,6 +394,40 @@ typedef struct fg_image_key_groups {
                                   * rows [first_row[s*maxp+g], first_row[s*maxp+g+1]) */
 } fg_image_key_groups;
 int  fg_snapshot_key_groups(fg_handle* h, fg_image_key_groups* out);
+/* Selective images (ABI 16, added): a checkpoint that exports and copies only the slices its caller
+ * needs. The engine says what is resident and what changed (plan), the caller answers with a mask
+ * (a shim's policy needs more than the changed slices: a CUMULATE namespace is rebuilt from all its
+ * contributing slices), the engine exports exactly the masked slices (select).
+ * fg_snapshot_plan: the front half of fg_snapshot_state -- pending fires settled, the staged records
+ * flushed, a pending restore re-fire finished, the region counts read -- without exporting or copying a
+ * row. `out` lists every resident slice, ascending: rows, first_row = the position the slice would have
+ * in a full fg_snapshot_state image taken now (the exclusive prefix of rows), changed as
+ * fg_snapshot_slices would report it; *timer_watermark (may be NULL) is what fg_snapshot_state would
+ * return. No changed flag is cleared, two plans in a row give the same answer. The arrays are valid
+ * until the next call on the handle. FG_ESTATE while an asynchronous snapshot is uncollected.
+ * fg_snapshot_state_select_async: exports the slices i with want[i] != 0 (indexed as in the plan) in
+ * one kernel launch and queues the image's copy as fg_snapshot_state_async does;
+ * fg_snapshot_state_wait collects it (one snapshot at a time, shared with fg_snapshot_state[_async]).
+ *  - FG_ESTATE unless the plan is still valid: fg_snapshot_plan, fg_get_stats, fg_late_dropped,
+ *    fg_kernel_stats, fg_set_kernel_timing, fg_synchronize, fg_stream and fg_last_error keep it valid,
+ *    every other call on the handle invalidates it, and a select consumes it. The image is therefore
+ *    the state as of the plan.
+ *  - FG_EINVAL before any device work (the handle stays usable, the plan stays valid): n differs from
+ *    the plan's n; want is NULL with n > 0; 2^32 or more selected rows.
+ *  - The image holds exactly the rows a full image holds for the selected slices (per slice the same
+ *    multiset), grouped by slice, ascending, compact from row 0. After the wait fg_snapshot_slices
+ *    describes that image: only the selected slices, first_row the compact prefix, changed as planned.
+ *    With fg_set_snapshot_grouping on each selected slice's rows are ordered by key group and
+ *    fg_snapshot_key_groups indexes the compact image (n_slices = the selected slices).
+ *  - changed is cleared only for the selected slices: a changed slice left out is reported changed
+ *    again by the next plan.
+ *  - An all-zero mask, or a handle without slices (n == 0, want may be NULL), gives a valid image with
+ *    n == 0. cnt_val may alias cnt_star as for fg_snapshot_state_async.
+ * fg_snapshot_state_select is _select_async + _wait. */
+int  fg_snapshot_plan(fg_handle* h, fg_image_slices* out, int64_t* timer_watermark);
+int  fg_snapshot_state_select_async(fg_handle* h, const uint8_t* want, int64_t n);
+int  fg_snapshot_state_select(fg_handle* h, const uint8_t* want, int64_t n, fg_state_rows* out,
+                              int64_t* timer_watermark);
 /* The device self-check (ABI 16): the DPP wave scans and the tile walk the fire runs, as this
  * library's code object compiled them, on inputs whose answers the host knows (msg: "ok" or what is
  * wrong). fg_open runs it once per process and device and fails with FG_EDEVICE (its message in

@@ -117,6 +117,21 @@ public final class FlinkGpu {
     public static native long[] snapshotSlices(long h);
 
     /**
+     * fg_snapshot_plan (ABI 16): every resident slice, laid out as snapshotSlices returns an image's
+     * slices ([n, sliceEnd[n], firstRow[n], rows[n], changed[n]]; firstRow: the slice's place in a full
+     * image taken now), without exporting or copying a row; timerWatermark[0] as snapshotState returns
+     * it. Valid for snapshotSelectAsync until any other call that may change the handle's state.
+     */
+    public static native long[] snapshotPlan(long h, long[] timerWatermark);
+
+    /**
+     * fg_snapshot_state_select_async: the planned slices i with want[i] != 0 (one long per planned
+     * slice) exported (one kernel launch) and their copy to the host image queued; snapshotStateWait collects the image, and
+     * snapshotSlices then lists the selected slices with compact firstRow.
+     */
+    public static native void snapshotSelectAsync(long h, long[] want);
+
+    /**
      * fg_set_snapshot_grouping: from the next snapshot on, the rows of every slice of an image are
      * ordered by key group (keyHash, the handle's max parallelism), partitioned on the GPU before
      * the image leaves it; keyHash &lt; 0 turns the grouping off.

@@ -18,7 +18,7 @@
  *                       the watermark (SlicingWindowOperator.java:207-210)
  *   advanceAsync / collectHeld   fg_advance_progress_async + fg_collect_fired for an operator that
  *                       holds the watermark while the fires complete (GpuSlicingWindowAggOperator)
- *   prepareCheckpoint   fg_flush + fg_snapshot_state_async / _wait: the resident accumulators are written to the
+ *   prepareCheckpoint   fg_flush + fg_snapshot_plan / fg_snapshot_state_select_async / _wait: the resident accumulators are written to the
  *                       reference's own keyed state "window-aggs" (namespace = slice end, the
  *                       accumulator row in the accSerializer layout, GpuAccRows) and the window
  *                       timers AggCombiner would hold are registered -- a savepoint the reference
@@ -337,9 +337,6 @@ public final class GpuSlicingWindowProcessor implements SlicingWindowProcessor<L
             FlinkGpu.snapshotStateWait(handle, new ByteBuffer[7], new long[1]);
             snapshotPending = false;
         }
-        // the image's export and host copy run on the GPU while the previous image is cleared
-        FlinkGpu.snapshotStateAsync(handle);
-        snapshotPending = true;
         writeKeyedState();
     }
 
@@ -362,32 +359,32 @@ public final class GpuSlicingWindowProcessor implements SlicingWindowProcessor<L
      *    after the progress (fireWindow's nextTriggerWindow registration): registered for the keys of
      *    rewritten namespaces, and for every such key when that next window end moved.
      * Round 5 cleared every entry, deleted every timer and wrote the whole image at every barrier on
-     * the task thread. Mirror: flink_amd/keyed_state.py (tests/test_gpu_incremental_state.py checks
-     * it against that full rewrite, and a failover restored from the written backend).
+     * the task thread.
+     *
+     * <p>The image is selective: fg_snapshot_plan lists the resident slices and which changed (no row
+     * exported or copied), the policy above picks the slices of the namespaces to rewrite, and
+     * fg_snapshot_state_select_async exports and copies exactly those (one kernel launch, while the
+     * namespaces to clear are cleared). The keys of fired slices left out of the image -- needed for the
+     * next-window timers when the next window end moved -- come from the backend's own entries of
+     * their namespaces: an unselected slice is unchanged, so the backend holds its keys.
+     * Mirror: flink_amd/keyed_state.py wanted_slices / write_delta (tests/test_gpu_snapshot_select.py
+     * checks it against the full rewrite, and a failover restored from the written backend).
      */
     private void writeKeyedState() throws Exception {
         KeyedStateBackend<RowData> backend = ctx.getKeyedStateBackend();
-        ByteBuffer[] cols = new ByteBuffer[7];
         long[] wm = new long[1];
-        FlinkGpu.snapshotStateWait(handle, cols, wm);
-        snapshotPending = false;
-        for (ByteBuffer c : cols) {
-            if (c != null) {
-                c.order(ByteOrder.nativeOrder());
-            }
-        }
+        final long[] plan = FlinkGpu.snapshotPlan(handle, wm);   // [n, slice_end, first_row, rows, changed]
         final long progress = wm[0];
-        final long[] sl = FlinkGpu.snapshotSlices(handle);
-        final int ns = (int) sl[0];
-        // namespaces of the image: their slices, whether one changed
+        final int ns = (int) plan[0];
+        // namespaces of the resident slices: their slices, whether one changed
         Map<Long, Set<Long>> contrib = new HashMap<>();
         Map<Long, Boolean> changed = new HashMap<>();
         long[] nsOf = new long[ns];
         for (int i = 0; i < ns; i++) {
-            long slice = sl[1 + i];
+            long slice = plan[1 + i];
             nsOf[i] = namespaceOf(slice, progress);
             contrib.computeIfAbsent(nsOf[i], k -> new HashSet<>()).add(slice);
-            changed.merge(nsOf[i], sl[1 + 3 * ns + i] != 0, Boolean::logicalOr);
+            changed.merge(nsOf[i], plan[1 + 3 * ns + i] != 0, Boolean::logicalOr);
         }
         Set<Long> rebuild = new HashSet<>();
         for (Map.Entry<Long, Set<Long>> e : contrib.entrySet()) {
@@ -397,6 +394,15 @@ public final class GpuSlicingWindowProcessor implements SlicingWindowProcessor<L
                 changed.put(e.getKey(), true);
             }
         }
+        // the mask: every slice of a namespace to rewrite; nothing may touch the handle between the
+        // plan and the select
+        long[] want = new long[ns];
+        for (int i = 0; i < ns; i++) {
+            want[i] = changed.get(nsOf[i]) ? 1 : 0;
+        }
+        // the selected slices' export and host copy run on the GPU while the previous image is cleared
+        FlinkGpu.snapshotSelectAsync(handle, want);
+        snapshotPending = true;
         Set<Long> clear = new HashSet<>(rebuild);
         for (Long n : imageContrib.keySet()) {
             if (!contrib.containsKey(n)) {
@@ -410,31 +416,34 @@ public final class GpuSlicingWindowProcessor implements SlicingWindowProcessor<L
                 windowState.clear(n);
             }
         }
+        ByteBuffer[] cols = new ByteBuffer[7];
+        FlinkGpu.snapshotStateWait(handle, cols, wm);
+        snapshotPending = false;
+        for (ByteBuffer c : cols) {
+            if (c != null) {
+                c.order(ByteOrder.nativeOrder());
+            }
+        }
+        final long[] sl = FlinkGpu.snapshotSlices(handle);   // the selected slices, compact
+        final int nsel = (int) sl[0];
         long interval = windowInterval();
         long nextEnd =
                 TimeWindow.getWindowStartWithOffset(toUtcTimestampMills(progress, shiftTimeZone), spec.offsetMs, interval)
                         + interval;
         boolean nextMoved = nextEnd != lastNextEnd;
-        // the rows of the slices to read: those of rewritten namespaces, and of fired slices when the
-        // next window end moved (their keys' next-window timers)
+        // the image's rows: the slices of rewritten namespaces (a fired one's keys take the next-window timer)
         Map<Long, Map<BinaryRowData, RowData>> image = new HashMap<>();
-        Set<BinaryRowData> needNextTimer = new HashSet<>();
-        for (int i = 0; i < ns; i++) {
+        Set<RowData> needNextTimer = new HashSet<>();
+        for (int i = 0; i < nsel; i++) {
             long slice = sl[1 + i];
-            boolean write = changed.get(nsOf[i]);
+            long nsp = namespaceOf(slice, progress);
             boolean fired = isWindowFired(slice, progress, shiftTimeZone);
-            if (!write && !(fired && nextMoved)) {
-                continue;
-            }
-            int first = (int) sl[1 + ns + i], rows = (int) sl[1 + 2 * ns + i];
+            int first = (int) sl[1 + nsel + i], rows = (int) sl[1 + 2 * nsel + i];
             RowData[] keyRows = keys.rows(slice(cols[0], first, rows), rows);
             for (int r = 0; r < rows; r++) {
                 BinaryRowData key = (BinaryRowData) keyRows[r];
                 if (fired && !proctime()) {
                     needNextTimer.add(key);
-                }
-                if (!write) {
-                    continue;
                 }
                 int at = first + r;
                 GenericRowData acc =
@@ -444,9 +453,19 @@ public final class GpuSlicingWindowProcessor implements SlicingWindowProcessor<L
                                 cols[4].getLong(8 * at),
                                 cols[5] == null ? cols[4].getLong(8 * at) : cols[5].getLong(8 * at),
                                 cols[6] == null ? cols[4].getLong(8 * at) : cols[6].getLong(8 * at));
-                Map<BinaryRowData, RowData> m = image.computeIfAbsent(nsOf[i], k -> new HashMap<>());
+                Map<BinaryRowData, RowData> m = image.computeIfAbsent(nsp, k -> new HashMap<>());
                 RowData prev = m.get(key);
                 m.put(key, prev == null ? acc : accRows.merge(prev, acc));
+            }
+        }
+        // fired slices left out of the image, when the next window end moved: their keys are the
+        // backend's keys of their (unchanged) namespaces
+        if (nextMoved && !proctime()) {
+            Set<Long> scanned = new HashSet<>();
+            for (int i = 0; i < ns; i++) {
+                if (want[i] == 0 && isWindowFired(plan[1 + i], progress, shiftTimeZone) && scanned.add(nsOf[i])) {
+                    needNextTimer.addAll(backend.<Long>getKeys(STATE_NAME, nsOf[i]).collect(Collectors.toList()));
+                }
             }
         }
         for (Map.Entry<Long, Map<BinaryRowData, RowData>> e : image.entrySet()) {
@@ -460,7 +479,7 @@ public final class GpuSlicingWindowProcessor implements SlicingWindowProcessor<L
                 }
             }
         }
-        for (BinaryRowData key : needNextTimer) {
+        for (RowData key : needNextTimer) {
             backend.setCurrentKey(key);
             timerService.registerEventTimeWindowTimer(nextEnd);
         }

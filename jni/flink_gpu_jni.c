@@ -25,6 +25,8 @@
  *   hostRegister    fg_host_register     (page-lock a managed-memory segment at open: direct DMA)
  *   hostUnregister  fg_host_unregister   (at close)
  *   snapshotSlices  fg_snapshot_slices   (the image's slices and which changed: the incremental keyed-state write)
+ *   snapshotPlan / snapshotSelectAsync   fg_snapshot_plan / fg_snapshot_state_select_async (the resident
+ *                   slices, then an image of the masked ones only)
  *   snapshotGrouping / snapshotKeyGroups   fg_set_snapshot_grouping / fg_snapshot_key_groups (images ordered
  *                   by key group inside every slice, and the offsets: chunks cut along key groups)
  *   comm*           fg_comm_*            (the keyBy edge local -> global over RCCL: KeyGroupStreamPartitioner
@@ -311,6 +313,28 @@ JNIEXPORT jlong JNICALL FN(snapshotStateWait)(JNIEnv* env, jclass cls, jlong hp,
     return s.n;
 }
 
+/* [n, slice_end[n], first_row[n], rows[n], changed[n] (1 / 0)] of an fg_image_slices */
+static jlongArray slices_array(JNIEnv* env, const fg_image_slices* s, const char* what) {
+    const jsize n = (jsize)s->n;
+    jlongArray out = (*env)->NewLongArray(env, 1 + 4 * n);
+    if (!out) return NULL;
+    jlong* buf = (jlong*)malloc(sizeof(jlong) * (size_t)(1 + 4 * n));
+    if (!buf) {
+        throw_code(env, FG_EDEVICE, what);
+        return NULL;
+    }
+    buf[0] = n;
+    for (jsize i = 0; i < n; i++) {
+        buf[1 + i] = s->slice_end[i];
+        buf[1 + n + i] = s->first_row[i];
+        buf[1 + 2 * n + i] = s->rows[i];
+        buf[1 + 3 * n + i] = s->changed[i] ? 1 : 0;
+    }
+    (*env)->SetLongArrayRegion(env, out, 0, 1 + 4 * n, buf);
+    free(buf);
+    return out;
+}
+
 /* long[] snapshotSlices(long h): the slices of the image the last snapshotState / snapshotStateWait
  * returned (fg_snapshot_slices, ABI 16) as one array: [n, slice_end[n], first_row[n], rows[n],
  * changed[n] (1 / 0)] -- the shim rewrites only the changed slices' keyed state */
@@ -319,24 +343,44 @@ JNIEXPORT jlongArray JNICALL FN(snapshotSlices)(JNIEnv* env, jclass cls, jlong h
     fg_handle* h = (fg_handle*)(intptr_t)hp;
     fg_image_slices s;
     if (check(env, h, fg_snapshot_slices(h, &s))) return NULL;
-    const jsize n = (jsize)s.n;
-    jlongArray out = (*env)->NewLongArray(env, 1 + 4 * n);
-    if (!out) return NULL;
-    jlong* buf = (jlong*)malloc(sizeof(jlong) * (size_t)(1 + 4 * n));
-    if (!buf) {
-        throw_code(env, FG_EDEVICE, "snapshotSlices: out of host memory");
-        return NULL;
+    return slices_array(env, &s, "snapshotSlices: out of host memory");
+}
+
+/* long[] snapshotPlan(long h, long[] timerWatermark): every resident slice, laid out as snapshotSlices
+ * (fg_snapshot_plan, ABI 16): nothing exported or copied, no changed flag cleared */
+JNIEXPORT jlongArray JNICALL FN(snapshotPlan)(JNIEnv* env, jclass cls, jlong hp, jlongArray timerWm) {
+    (void)cls;
+    fg_handle* h = (fg_handle*)(intptr_t)hp;
+    fg_image_slices s;
+    int64_t wm = 0;
+    if (check(env, h, fg_snapshot_plan(h, &s, &wm))) return NULL;
+    jlong w = wm;
+    (*env)->SetLongArrayRegion(env, timerWm, 0, 1, &w);
+    return slices_array(env, &s, "snapshotPlan: out of host memory");
+}
+
+/* void snapshotSelectAsync(long h, long[] want): the planned slices with want[i] != 0 exported and
+ * their host copy queued (fg_snapshot_state_select_async); snapshotStateWait collects the image. The
+ * mask is one long per resident slice (a handful): the glue narrows it to the C-ABI's bytes. */
+JNIEXPORT void JNICALL FN(snapshotSelectAsync)(JNIEnv* env, jclass cls, jlong hp, jlongArray want) {
+    (void)cls;
+    fg_handle* h = (fg_handle*)(intptr_t)hp;
+    const jsize n = want ? (*env)->GetArrayLength(env, want) : 0;
+    uint8_t* mask = NULL;
+    if (n > 0) {
+        mask = (uint8_t*)malloc((size_t)n);
+        jlong* w = mask ? (*env)->GetLongArrayElements(env, want, NULL) : NULL;
+        if (!w) {
+            free(mask);
+            throw_code(env, FG_EDEVICE, "snapshotSelectAsync: out of host memory");
+            return;
+        }
+        for (jsize i = 0; i < n; i++) mask[i] = w[i] != 0;
+        (*env)->ReleaseLongArrayElements(env, want, w, JNI_ABORT);
     }
-    buf[0] = n;
-    for (jsize i = 0; i < n; i++) {
-        buf[1 + i] = s.slice_end[i];
-        buf[1 + n + i] = s.first_row[i];
-        buf[1 + 2 * n + i] = s.rows[i];
-        buf[1 + 3 * n + i] = s.changed[i] ? 1 : 0;
-    }
-    (*env)->SetLongArrayRegion(env, out, 0, 1 + 4 * n, buf);
-    free(buf);
-    return out;
+    const int rc = fg_snapshot_state_select_async(h, mask, n);
+    free(mask);
+    (void)check(env, h, rc);
 }
 
 /* void snapshotGrouping(long h, int keyHash): from the next snapshot on, every slice's rows of an image
