@@ -25,10 +25,13 @@
 // slot and the entry) and k_dict_verify (the byte comparison of the rows whose slot is new).
 // Reservations (miss and pending lists, ids, arena bytes) take one atomic per wave. A 64-bit
 // tag shared by distinct rows fails the comparison and is resolved on the host, so ids stay
-// exact whatever the hash.
+// exact whatever the hash. The way out is fg_key_dict_rows: the packed key rows of ids, gathered
+// by k_rows_* (lengths and a 64-bit scan for the offsets, one host read, then a copy balanced by
+// bytes) -- fired rows, checkpoints and a rescale's re-intern copy those rows, never an arena range.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -484,6 +487,127 @@ __global__ __launch_bounds__(kDictThreads) void k_dict_gather(DictDev d, int64_t
     len_out[i] = ok ? d.ent_len[ord] : -1;
 }
 
+// ---- fg_key_dict_rows: the packed key rows of ids (the layout fg_key_dict_intern reads) ----
+//
+// Ids are taken in blocks of kRowsBlock. Lengths and offsets: k_rows_lengths (the ordinal check,
+// out_lengths, each block's padded bytes), k_rows_scan_sums (one workgroup: the exclusive scan of
+// the block sums, the total) and k_rows_offsets (out_offsets[0..n)); 64-bit throughout. The host
+// reads RowsCtr once, checks the capacity and the bad ids, and only then launches k_rows_copy.
+constexpr int kRowsBlock = kDictThreads;   // ids per scan block = rows per copy workgroup
+
+struct RowsCtr {
+    unsigned long long total;      // padded bytes of every row = out_offsets[n]
+    unsigned long long bad;        // ids that are negative or past the dictionary's size
+    unsigned long long bad_first;  // lowest index of such an id (~0: none)
+};
+
+__host__ __device__ __forceinline__ uint64_t padded8(int32_t len) { return ((uint64_t)(uint32_t)len + 7) & ~7ull; }
+
+// exclusive scan of v over the workgroup (s_wave: kDictThreads / 64 words, reusable on return)
+__device__ __forceinline__ uint64_t block_exclusive_scan_u64(uint64_t v, uint64_t* s_wave, uint64_t* total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint64_t x = v;   // inclusive scan over the wave
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint64_t y = __shfl_up(x, off);
+        if (lane >= off) x += y;
+    }
+    if (lane == 63) s_wave[wave] = x;
+    __syncthreads();
+    uint64_t base = 0, t = 0;
+#pragma unroll
+    for (int k = 0; k < kDictThreads / 64; k++) {
+        const uint64_t w = s_wave[k];
+        if (k < wave) base += w;
+        t += w;
+    }
+    __syncthreads();
+    *total = t;
+    return base + x - v;
+}
+
+__global__ __launch_bounds__(kDictThreads) void k_rows_lengths(DictDev d, int64_t nids, int64_t n, const int64_t* ids,
+                                                               int32_t* len_out, uint64_t* sums, RowsCtr* rc) {
+    __shared__ uint64_t s_wave[kDictThreads / 64];
+    const int64_t i = (int64_t)blockIdx.x * kRowsBlock + threadIdx.x;
+    const bool valid = i < n;
+    const int64_t id = valid ? ids[i] : 0;
+    const uint64_t ord = (uint64_t)id >> d.kg_bits;
+    const bool ok = valid && id >= 0 && (int64_t)ord < nids;
+    const int32_t len = ok ? d.ent_len[ord] : 0;
+    if (valid) len_out[i] = ok ? len : -1;
+    const unsigned long long badm = __ballot(valid && !ok);   // (one atomic pair per wave holding a bad id)
+    if (badm && (threadIdx.x & 63) == 0) {
+        atomicAdd(&rc->bad, (unsigned long long)__popcll(badm));
+        atomicMin(&rc->bad_first, (unsigned long long)(i + __ffsll((long long)badm) - 1));
+    }
+    uint64_t total;
+    (void)block_exclusive_scan_u64(padded8(len), s_wave, &total);
+    if (threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+
+// one workgroup: sums[0..nb) -> their exclusive scan, the total to rc->total and off_out[n]
+__global__ __launch_bounds__(kDictThreads) void k_rows_scan_sums(uint64_t* sums, int64_t nb, RowsCtr* rc, int64_t* off_out,
+                                                                 int64_t n) {
+    __shared__ uint64_t s_wave[kDictThreads / 64];
+    uint64_t carry = 0;   // (the same in every thread)
+    for (int64_t b0 = 0; b0 < nb; b0 += kDictThreads) {
+        const int64_t b = b0 + threadIdx.x;
+        uint64_t total;
+        const uint64_t ex = block_exclusive_scan_u64(b < nb ? sums[b] : 0ull, s_wave, &total);
+        if (b < nb) sums[b] = carry + ex;
+        carry += total;
+    }
+    if (threadIdx.x == 0) {
+        rc->total = carry;
+        off_out[n] = (int64_t)carry;
+    }
+}
+
+__global__ __launch_bounds__(kDictThreads) void k_rows_offsets(int64_t n, const int32_t* len_in, const uint64_t* sums,
+                                                               int64_t* off_out) {
+    __shared__ uint64_t s_wave[kDictThreads / 64];
+    const int64_t i = (int64_t)blockIdx.x * kRowsBlock + threadIdx.x;
+    const int32_t len = i < n ? len_in[i] : 0;
+    uint64_t total;
+    const uint64_t ex = block_exclusive_scan_u64(len > 0 ? padded8(len) : 0ull, s_wave, &total);
+    if (i < n) off_out[i] = (int64_t)(sums[blockIdx.x] + ex);
+}
+
+// The copy, balanced by bytes: a workgroup owns kRowsBlock consecutive rows, whose output span
+// [off[r0], off[r0 + m]) is contiguous; its threads stride over the span's 8-byte words, so the
+// stores are coalesced and no lane idles because its row is short. A word finds its row by a
+// binary search over the run's offsets in LDS (the last row starting at or before it: empty rows
+// share their successor's offset and are never picked) and loads the word at the same distance
+// into that row's arena entry -- rows are 8-byte aligned and zero-padded to 8 in the arena, so
+// whole words, pad included, are right. Launched only after the host has seen every id good and
+// the total within the caller's capacity; an ordinal is still checked against nids (zero words).
+__global__ __launch_bounds__(kDictThreads) void k_rows_copy(DictDev d, int64_t nids, int64_t n, const int64_t* ids,
+                                                            const int64_t* off, uint64_t* out, int64_t out_words) {
+    __shared__ int64_t s_off[kRowsBlock + 1];
+    __shared__ int64_t s_src[kRowsBlock];
+    const int64_t r0 = (int64_t)blockIdx.x * kRowsBlock;
+    const int m = (int)(n - r0 < kRowsBlock ? n - r0 : kRowsBlock);
+    if ((int)threadIdx.x < m) {
+        const int64_t id = ids[r0 + threadIdx.x];
+        const uint64_t ord = (uint64_t)id >> d.kg_bits;
+        s_off[threadIdx.x] = off[r0 + threadIdx.x];
+        s_src[threadIdx.x] = (id >= 0 && (int64_t)ord < nids) ? d.ent_off[ord] : -1;
+    }
+    if (threadIdx.x == 0) s_off[m] = off[r0 + m];
+    __syncthreads();
+    const int64_t w1 = s_off[m] >> 3 < out_words ? s_off[m] >> 3 : out_words;
+    for (int64_t w = (s_off[0] >> 3) + threadIdx.x; w < w1; w += kDictThreads) {
+        const int64_t b = w << 3;
+        int lo = 0, hi = m;   // s_off[lo] <= b < s_off[hi]
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (s_off[mid] <= b) lo = mid; else hi = mid;
+        }
+        const int64_t src = s_src[lo];
+        out[w] = src >= 0 ? *reinterpret_cast<const uint64_t*>(d.arena + src + (b - s_off[lo])) : 0ull;
+    }
+}
+
 __global__ __launch_bounds__(kDictThreads) void k_slots_clear(Slot* p, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * kDictThreads + threadIdx.x;
     if (i < n) {
@@ -540,13 +664,17 @@ struct fg_key_dict {
     int64_t arena_used = 0;
     Buf slots, slot_row, ent_off, ent_len, ent_tag, arena, counters;
     Buf in_bytes, in_off, in_len, row_tag, row_kg, row_slot, row_pkg, row_id, miss;   // per-call scratch
+    // fg_key_dict_rows: its counters (RowsCtr), the block sums, and for FG_HOST callers the device
+    // ids, lengths, offsets and packed bytes; grown on demand and reused across calls
+    Buf rows_ctr, rows_sums, rows_ids, rows_len, rows_off, rows_bytes;
     std::unordered_map<std::string, int64_t> side;   // rows whose tag another row holds
     std::string err;
     // kernel timing (fg_key_dict_set_timing): HIP events around each chunk's probe and its
-    // assign + verify, on the dictionary's stream; summed into the two classes below
+    // assign + verify, and around the two kernel stages of fg_key_dict_rows (ev[3..6]), on the
+    // dictionary's stream; summed into the three classes below
     bool timing = false;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    fg_kernel_stat kstat[2] = {};
+    hipEvent_t ev[7] = {};
+    fg_kernel_stat kstat[3] = {};
     // fg_key_dict_intern_async: the lookup launched, the rest of the call taken by _wait
     struct Pending {
         bool active = false, host = false;
@@ -930,6 +1058,109 @@ int fg_key_dict_lookup(fg_key_dict* d, int32_t location, int64_t n, const int64_
     return FG_OK;
 }
 
+int fg_key_dict_rows(fg_key_dict* d, int32_t location, int64_t n, const int64_t* ids, uint8_t* out_bytes,
+                     int64_t cap_bytes, int64_t* out_offsets, int32_t* out_lengths, int64_t* out_nbytes) {
+    if (!d) return FG_EINVAL;
+    if (location != FG_HOST && location != FG_DEVICE) return d->fail(FG_EINVAL, "fg_key_dict_rows: unknown location");
+    if (n < 0 || n > 0x7fffffff || cap_bytes < 0 || (cap_bytes > 0 && !out_bytes) ||
+        (n > 0 && (!ids || !out_offsets || !out_lengths || !out_nbytes)))
+        return d->fail(FG_EINVAL, "fg_key_dict_rows: invalid arguments");
+    const bool host = location == FG_HOST;
+    if (!host && (uintptr_t)out_bytes % 8 != 0)
+        return d->fail(FG_EINVAL, "fg_key_dict_rows: a device out_bytes must be 8-byte aligned");
+    if (d->pend.active) return d->fail(FG_ESTATE, "fg_key_dict_rows: an async intern is pending (fg_key_dict_intern_wait)");
+    if (n == 0) {
+        if (out_nbytes) *out_nbytes = 0;
+        if (out_offsets && host) out_offsets[0] = 0;
+        if (out_offsets && !host) {   // (a device word: the only device work of an empty call)
+            if (hipSetDevice(d->device) != hipSuccess) return d->fail(FG_EDEVICE, "hipSetDevice failed");
+            DCHK(d, hipMemsetAsync(out_offsets, 0, 8, d->stream));
+            DCHK(d, hipStreamSynchronize(d->stream));
+        }
+        return FG_OK;
+    }
+    if (hipSetDevice(d->device) != hipSuccess) return d->fail(FG_EDEVICE, "hipSetDevice failed");
+    hipStream_t s = d->stream;
+    const int64_t nb = (n + kRowsBlock - 1) / kRowsBlock;
+    DCHK(d, d->rows_ctr.ensure(sizeof(RowsCtr), s));
+    DCHK(d, d->rows_sums.ensure(8 * (size_t)nb, s));
+    const int64_t* di = ids;
+    int64_t* doff = out_offsets;
+    int32_t* dlen = out_lengths;
+    if (host) {
+        DCHK(d, d->rows_ids.ensure(8 * (size_t)n, s));
+        DCHK(d, d->rows_off.ensure(8 * (size_t)(n + 1), s));
+        DCHK(d, d->rows_len.ensure(4 * (size_t)n, s));
+        DCHK(d, hipMemcpyAsync(d->rows_ids.p, ids, 8 * (size_t)n, hipMemcpyHostToDevice, s));
+        di = d->rows_ids.as<int64_t>();
+        doff = d->rows_off.as<int64_t>();
+        dlen = d->rows_len.as<int32_t>();
+    }
+    // 1) lengths and offsets; then the one host read of the call: {total, bad ids, lowest bad index}
+    RowsCtr* rc = d->rows_ctr.as<RowsCtr>();
+    uint64_t* sums = d->rows_sums.as<uint64_t>();
+    const DictDev dv = d->dev();
+    DCHK(d, hipMemsetAsync(rc, 0, offsetof(RowsCtr, bad_first), s));
+    DCHK(d, hipMemsetAsync(&rc->bad_first, 0xff, 8, s));
+    if (d->timing) DCHK(d, hipEventRecord(d->ev[3], s));
+    hipLaunchKernelGGL(k_rows_lengths, dim3((unsigned)nb), dim3(kDictThreads), 0, s, dv, d->nids, n, di, dlen, sums, rc);
+    hipLaunchKernelGGL(k_rows_scan_sums, dim3(1), dim3(kDictThreads), 0, s, sums, nb, rc, doff, n);
+    hipLaunchKernelGGL(k_rows_offsets, dim3((unsigned)nb), dim3(kDictThreads), 0, s, n, dlen, sums, doff);
+    if (d->timing) DCHK(d, hipEventRecord(d->ev[4], s));
+    DCHK(d, hipGetLastError());
+    RowsCtr hc;
+    DCHK(d, hipMemcpyAsync(&hc, rc, sizeof hc, hipMemcpyDeviceToHost, s));
+    DCHK(d, hipStreamSynchronize(s));
+    float ms = 0.f;
+    if (d->timing) DCHK(d, hipEventElapsedTime(&ms, d->ev[3], d->ev[4]));
+    auto timed = [&](float t) {
+        if (!d->timing) return;
+        d->kstat[2].launches++;
+        d->kstat[2].total_ms += t;
+        d->kstat[2].records += n;
+    };
+    if (hc.bad) {
+        timed(ms);
+        return d->fail(FG_EINVAL, "fg_key_dict_rows: " + std::to_string(hc.bad) +
+                                      " unknown ids (negative, or not below the dictionary's size); the first at index " +
+                                      std::to_string(hc.bad_first));
+    }
+    const int64_t total = (int64_t)hc.total;
+    *out_nbytes = total;
+    if (host) {   // straight into the caller's memory (pinned or pageable): no staging of our own
+        DCHK(d, hipMemcpyAsync(out_offsets, doff, 8 * (size_t)(n + 1), hipMemcpyDeviceToHost, s));
+        DCHK(d, hipMemcpyAsync(out_lengths, dlen, 4 * (size_t)n, hipMemcpyDeviceToHost, s));
+    }
+    if (total > cap_bytes) {
+        if (host) DCHK(d, hipStreamSynchronize(s));
+        timed(ms);
+        return d->fail(FG_EFULL, "fg_key_dict_rows: the rows take " + std::to_string(total) + " bytes, out_bytes holds " +
+                                     std::to_string(cap_bytes));
+    }
+    // 2) the copy: total <= cap_bytes and every id is good
+    if (total > 0) {
+        uint8_t* dbytes = out_bytes;
+        if (host) {
+            DCHK(d, d->rows_bytes.ensure((size_t)total, s));
+            dbytes = d->rows_bytes.as<uint8_t>();
+        }
+        if (d->timing) DCHK(d, hipEventRecord(d->ev[5], s));
+        hipLaunchKernelGGL(k_rows_copy, dim3((unsigned)nb), dim3(kDictThreads), 0, s, dv, d->nids, n, di, doff,
+                           reinterpret_cast<uint64_t*>(dbytes), total >> 3);
+        if (d->timing) DCHK(d, hipEventRecord(d->ev[6], s));
+        DCHK(d, hipGetLastError());
+        if (host) DCHK(d, hipMemcpyAsync(out_bytes, dbytes, (size_t)total, hipMemcpyDeviceToHost, s));
+    }
+    DCHK(d, hipStreamSynchronize(s));
+    if (d->timing && total > 0) {
+        float ms2 = 0.f;
+        DCHK(d, hipEventElapsedTime(&ms2, d->ev[5], d->ev[6]));
+        ms += ms2;
+    }
+    timed(ms);
+    return FG_OK;
+}
+
 int fg_key_dict_arena(fg_key_dict* d, const uint8_t** dev_bytes, int64_t* size) {
     if (!d || !dev_bytes || !size) return FG_EINVAL;
     *dev_bytes = d->arena.as<uint8_t>();
@@ -959,6 +1190,7 @@ int fg_key_dict_set_timing(fg_key_dict* d, int32_t on) {
         for (auto& e : d->ev) DCHK(d, hipEventCreate(&e));
         std::snprintf(d->kstat[0].name, sizeof d->kstat[0].name, "dict_probe");
         std::snprintf(d->kstat[1].name, sizeof d->kstat[1].name, "dict_assign");
+        std::snprintf(d->kstat[2].name, sizeof d->kstat[2].name, "dict_rows");
     }
     d->timing = on != 0;
     return FG_OK;
@@ -966,7 +1198,7 @@ int fg_key_dict_set_timing(fg_key_dict* d, int32_t on) {
 
 int fg_key_dict_kernel_stats(fg_key_dict* d, fg_kernel_stat* out, int32_t max, int32_t* count) {
     if (!d || !count || (max > 0 && !out)) return FG_EINVAL;
-    *count = d->ev[0] ? 2 : 0;
+    *count = d->ev[0] ? 3 : 0;
     for (int i = 0; i < *count && i < max; i++) out[i] = d->kstat[i];
     return FG_OK;
 }

@@ -7,8 +7,9 @@ TC/data/binary/BinarySection.java:62-73) and the key group is
 murmurHash(hashBytesByWords(row)) % maxParallelism (BinarySection.hashCode :76-78,
 KeyGroupRangeAssignment.java:63-77). `KeyDictionary.intern` maps such rows to 64-bit ids on the
 GPU (equal rows -> equal ids, exact), which the window operators aggregate as BIGINT keys;
-`lookup` maps fired rows' ids back to the key rows. `key_row` / `decode_key_row` write and read
-key rows the way BinaryRowWriter does (writer/BinaryRowWriter.java, AbstractBinaryWriter.java:
+`rows` gathers the packed key rows of ids on the GPU (fired rows, checkpoints; `lookup` is its
+list-of-bytes form) and `reintern` carries ids from one dictionary into another (rescale).
+`key_row` / `decode_key_row` write and read key rows the way BinaryRowWriter does (writer/BinaryRowWriter.java, AbstractBinaryWriter.java:
 81-105,280-330: STRING of <= 7 bytes inline in its 8-byte slot as 0x80|len in the top byte,
 longer ones in the variable part, 8-byte aligned, the slot holding offset << 32 | length).
 """
@@ -237,29 +238,64 @@ class KeyDictionary:
         arena = torch.as_tensor(_Arena(), device=ids.device)
         return off // 4, (ln // 4).to(torch.int64), arena
 
+    def rows(self, ids):
+        """fg_key_dict_rows: the key rows of the ids, packed in their order the way pack_key_rows
+        packs them: (bytes u8[nbytes], offsets i64[n + 1], lengths i32[n]); row i is
+        bytes[offsets[i] : offsets[i] + lengths[i]], padded with zeros to 8 bytes. Numpy ids give
+        numpy arrays; a torch device tensor gives device tensors (no key byte touches the host).
+        At most two C calls: a guess of 32 bytes per row, one retry at the exact size if the rows
+        take more. Unknown ids raise KeyError."""
+        dev = hasattr(ids, "data_ptr")
+        if dev:
+            import torch
+            ids = ids.to(torch.int64).contiguous()
+            n = ids.numel()
+            ext = self.__dict__.get("_ext_stream")
+            if ext is None or ext.device != ids.device:
+                ext = self._ext_stream = torch.cuda.ExternalStream(self._lib.fg_key_dict_stream(self._h),
+                                                                   device=ids.device)
+            ext.wait_stream(torch.cuda.current_stream(ids.device))   # the ids' producer first
+            off = torch.empty(n + 1, dtype=torch.int64, device=ids.device)
+            ln = torch.empty(n, dtype=torch.int32, device=ids.device)
+            alloc = lambda cap: torch.empty(cap, dtype=torch.uint8, device=ids.device)   # noqa: E731
+            ptr = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
+            if n == 0:
+                off.zero_()
+        else:
+            ids = np.ascontiguousarray(ids, dtype=np.int64)
+            n = len(ids)
+            off = np.zeros(n + 1, dtype=np.int64)
+            ln = np.empty(n, dtype=np.int32)
+            alloc = lambda cap: np.empty(cap, dtype=np.uint8)   # noqa: E731
+            ptr = lambda a: C.c_void_p(a.ctypes.data)   # noqa: E731
+        if n == 0:
+            return alloc(0), off, ln
+        nbytes = C.c_int64()
+        cap = 32 * n
+        for _ in range(2):
+            buf = alloc(max(cap, 8))
+            rc = self._lib.fg_key_dict_rows(self._h, L.DEVICE if dev else L.HOST, n, ptr(ids), ptr(buf), cap, ptr(off),
+                                            ptr(ln), C.byref(nbytes))
+            if rc != L.FG_EFULL:
+                break
+            cap = int(nbytes.value)
+        if rc == L.FG_EINVAL:   # (the arguments above are well formed: an unknown id)
+            raise KeyError(self._lib.fg_key_dict_last_error(self._h).decode(errors="replace"))
+        self._check(rc)
+        return buf[:int(nbytes.value)], off, ln
+
     def lookup(self, ids):
         """Key rows (bytes) of the ids (host)."""
-        ids = np.ascontiguousarray(ids, dtype=np.int64)
-        n = len(ids)
-        if n == 0:
-            return []
-        off = np.empty(n, dtype=np.int64)
-        ln = np.empty(n, dtype=np.int32)
-        self._check(self._lib.fg_key_dict_lookup(self._h, L.HOST, n, ids.ctypes.data, off.ctypes.data, ln.ctypes.data))
-        if (ln < 0).any():
-            raise KeyError(f"unknown dictionary id {int(ids[np.argmax(ln < 0)])}")
-        lo, hi = int(off.min()), int((off + ln).max())
-        arena = np.empty(max(hi - lo, 1), dtype=np.uint8)
-        self._check(self._lib.fg_key_dict_copy_arena(self._h, lo, hi - lo, arena.ctypes.data))
-        raw = arena.tobytes()
-        return [raw[o - lo:o - lo + n_] for o, n_ in zip(off.tolist(), ln.tolist())]
+        buf, off, ln = self.rows(np.ascontiguousarray(ids, dtype=np.int64))
+        raw = buf.tobytes()
+        return [raw[o:o + n_] for o, n_ in zip(off[:-1].tolist(), ln.tolist())]
 
     def set_timing(self, on: bool = True):
         """HIP-event timing of the dictionary's kernels (kernel_stats)."""
         self._check(self._lib.fg_key_dict_set_timing(self._h, 1 if on else 0))
 
     def kernel_stats(self) -> dict:
-        """{"dict_probe" | "dict_assign": dict(launches, total_ms, records, rows)}."""
+        """{"dict_probe" | "dict_assign" | "dict_rows": dict(launches, total_ms, records, rows)}."""
         arr = (L.FgKernelStat * 4)()
         n = C.c_int32()
         self._check(self._lib.fg_key_dict_kernel_stats(self._h, arr, 4, C.byref(n)))
@@ -279,3 +315,15 @@ class KeyDictionary:
             self.close()
         except Exception:
             pass
+
+
+def reintern(ids, src: KeyDictionary, dst: KeyDictionary):
+    """The ids in `dst` of the key rows that `ids` name in `src`: src.rows(ids) interned by dst,
+    device to device when `ids` is a device tensor. Ids of one subtask's dictionary mean nothing
+    to another's, so a rescaled subtask maps the key column of every old subtask's image into its
+    own dictionary before restore_state_range(..., key_hash=KEYHASH_DICT_ID)."""
+    buf, off, ln = src.rows(ids)
+    if len(buf) == 0:   # (only empty rows, or none: the intern still wants a buffer to point at)
+        buf = buf.new_zeros(8) if hasattr(buf, "data_ptr") else np.zeros(8, dtype=np.uint8)
+    new_ids, _ = dst.intern(packed=(buf, off[:-1], ln), key_groups=False)
+    return new_ids

@@ -604,7 +604,7 @@ void fg_comm_close(fg_comm* c);
  * is resolved by comparing the bytes), id = ordinal << ceil(log2(max_parallelism)) | key group (below
  * 2^31 for 16.7M keys at max parallelism 128, so the window engine stages them as 32-bit keys). The ids are the BIGINT key
  * column of fg_add_batch / the key field of fg_add_rows; FG_KEYHASH_DICT_ID routes them by the
- * carried key group; fired rows' ids map back to their rows with fg_key_dict_lookup. A handle is
+ * carried key group; fired rows' ids map back to their rows with fg_key_dict_rows. A handle is
  * single-threaded like fg_handle; ids are stable for the dictionary's life (a restored operator
  * re-interns the key rows of its state image first). */
 typedef struct fg_key_dict fg_key_dict;
@@ -629,13 +629,47 @@ int  fg_key_dict_intern_wait(fg_key_dict* d);
 /* For each id: its row's offset and length in the dictionary's arena (-1 / -1 for an unknown id). */
 int  fg_key_dict_lookup(fg_key_dict* d, int32_t location, int64_t n, const int64_t* ids, int64_t* out_offsets,
                         int32_t* out_lengths);
+/* The key rows of n ids, packed, in the order of the ids (ABI 16, added): the way out of the
+ * dictionary, one gather on the device instead of fg_key_dict_lookup + a copy of the arena range
+ * the ids span. The layout is the one fg_key_dict_intern reads, so the output of one dictionary
+ * is valid input to the intern of another (rescale: a new subtask re-interns the key rows of
+ * every old image):
+ *   row i = out_bytes[out_offsets[i], out_offsets[i] + out_lengths[i]);
+ *   out_offsets has n + 1 entries: out_offsets[0] = 0, out_offsets[i + 1] = out_offsets[i] +
+ *   ((out_lengths[i] + 7) & ~7), out_offsets[n] = *out_nbytes; the pad bytes are zero (zero
+ *   padding to 8); a repeated id gets a copy of its row per occurrence.
+ * location is FG_HOST (ids and the three outputs are host memory, pageable or pinned: the packed
+ * bytes, the offsets and the lengths are copied straight into them -- 8 + 12 n + *out_nbytes
+ * bytes and one 24-byte read of the call's counters cross to the host, no arena range) or
+ * FG_DEVICE (all four are device pointers, read and written on the dictionary's stream under
+ * the ordering rule of fg_key_dict_intern; out_bytes 8-byte aligned). out_nbytes is always a
+ * host pointer. The outputs are complete when the call returns. Returns
+ *   FG_EFULL   *out_nbytes > cap_bytes: out_offsets, out_lengths and *out_nbytes are complete,
+ *              out_bytes is untouched; call again with a larger buffer. out_bytes NULL with
+ *              cap_bytes 0 is the sizing call;
+ *   FG_EINVAL  before any device work: a NULL dictionary, n < 0 or n > 2^31 - 1, n > 0 with a
+ *              NULL ids / out_offsets / out_lengths / out_nbytes, cap_bytes < 0, cap_bytes > 0
+ *              with a NULL out_bytes, an unknown location, a misaligned device out_bytes;
+ *   FG_EINVAL  after the length pass: an id that is negative or whose ordinal is not below
+ *              fg_key_dict_size -- the message gives how many and the lowest such index;
+ *              nothing is written to out_bytes;
+ *   FG_ESTATE  while an async intern is pending, as fg_key_dict_lookup.
+ * n == 0: FG_OK, *out_nbytes = 0, out_offsets[0] = 0 if out_offsets is non-NULL (no kernel runs;
+ * a device out_offsets takes one 8-byte memset). The dictionary is not modified and stays usable
+ * after every error. Rows of any length up to the intern's limit (2^24 - 4 bytes) come out
+ * right; one very long row is copied by a single workgroup. */
+int  fg_key_dict_rows(fg_key_dict* d, int32_t location, int64_t n, const int64_t* ids,
+                      uint8_t* out_bytes, int64_t cap_bytes,
+                      int64_t* out_offsets /* [n + 1] */, int32_t* out_lengths /* [n] */,
+                      int64_t* out_nbytes /* always a host pointer */);
 /* The arena (device memory, rows padded to 8 bytes) and its used size; valid until the next intern. */
 int  fg_key_dict_arena(fg_key_dict* d, const uint8_t** dev_bytes, int64_t* size);
 int  fg_key_dict_copy_arena(fg_key_dict* d, int64_t begin, int64_t nbytes, uint8_t* host);
 int64_t fg_key_dict_size(fg_key_dict* d);   /* distinct key rows interned */
 void* fg_key_dict_stream(fg_key_dict* d);   /* the dictionary's device stream (hipStream_t) */
 /* HIP-event timing of the dictionary's kernels (per chunk: "dict_probe", then "dict_assign" =
- * assign + verify of the rows new in the chunk); fg_key_dict_kernel_stats copies them. */
+ * assign + verify of the rows new in the chunk; per fg_key_dict_rows call: "dict_rows" = all of
+ * the call's kernels, records = its ids); fg_key_dict_kernel_stats copies them. */
 int  fg_key_dict_set_timing(fg_key_dict* d, int32_t on);
 int  fg_key_dict_kernel_stats(fg_key_dict* d, fg_kernel_stat* out, int32_t max, int32_t* count);
 const char* fg_key_dict_last_error(fg_key_dict* d);

@@ -201,6 +201,22 @@ public final class FlinkGpu {
     public static native void dictLookup(
             long d, ByteBuffer ids, int n, ByteBuffer outOffsets, ByteBuffer outLengths);
 
+    /**
+     * fg_key_dict_rows (FG_HOST): the key rows of ids[0 .. n), packed in their order into
+     * outBytes (row i at outOffsets[i], outLengths[i] bytes, padded with zeros to 8; outOffsets
+     * holds n + 1 longs). Returns the bytes the rows take. A result above capBytes means outBytes
+     * was too small and is untouched (outOffsets and outLengths are complete): grow it and call
+     * again. outBytes may be null with capBytes 0.
+     */
+    public static native long dictRows(
+            long d,
+            ByteBuffer ids,
+            int n,
+            ByteBuffer outBytes,
+            long capBytes,
+            ByteBuffer outOffsets,
+            ByteBuffer outLengths);
+
     /** fg_key_dict_copy_arena. */
     public static native void dictCopyArena(long d, long begin, long nbytes, ByteBuffer out);
 

@@ -5,8 +5,10 @@
  * BinarySection.equals / hashCode, BinarySection.java:62-78).
  *
  * Per micro-batch the key rows are gathered into one direct buffer and interned by ONE
- * dictIntern call; per advance the fired rows' ids become key rows through ONE dictLookup of
- * every id and ONE arena copy of the byte range they span -- never a JNI round trip per row.
+ * dictIntern call; per advance the fired rows' ids become key rows through ONE dictRows call:
+ * the GPU gathers exactly those rows, packed in the ids' order, and only they cross to the host
+ * (a second call when the reused buffer has to grow) -- never a JNI round trip per row, and no
+ * copy of the arena range the ids span.
  */
 package org.apache.flink.table.runtime.operators.window.gpu;
 
@@ -27,7 +29,7 @@ final class GpuKeyRows implements AutoCloseable {
     private ByteBuffer rows, offsets, lengths;   // the current micro-batch's key rows
     private int n;
     private int bytes;
-    private ByteBuffer ids, outOff, outLen;      // lookup scratch (grown on demand)
+    private ByteBuffer outBytes, outOff, outLen; // dictRows scratch (reused, grown on demand)
 
     GpuKeyRows(GpuWindowAggSpec spec, int maxParallelism) {
         this.bigint = spec.bigintKey;
@@ -87,7 +89,7 @@ final class GpuKeyRows implements AutoCloseable {
         bytes = 0;
     }
 
-    /** the key rows of ids keys[0 .. count) (one dictLookup, one arena copy) */
+    /** the key rows of ids keys[0 .. count) (one dictRows into the reused buffers) */
     RowData[] rows(ByteBuffer keys, int count) {
         RowData[] out = new RowData[count];
         if (bigint) {
@@ -106,25 +108,29 @@ final class GpuKeyRows implements AutoCloseable {
         if (count == 0) {
             return out;
         }
-        if (outOff == null || outOff.capacity() < 8 * count) {
-            outOff = direct(8L * count);
+        if (outOff == null || outOff.capacity() < 8L * (count + 1)) {
+            outOff = direct(8L * (count + 1));
             outLen = direct(4L * count);
         }
-        FlinkGpu.dictLookup(dict, keys, count, outOff, outLen);
-        long lo = Long.MAX_VALUE, hi = 0;
-        for (int i = 0; i < count; i++) {
-            long o = outOff.getLong(8 * i);
-            lo = Math.min(lo, o);
-            hi = Math.max(hi, o + outLen.getInt(4 * i));
+        if (outBytes == null) {
+            outBytes = direct(32L * count);
         }
-        ByteBuffer arena = direct(hi - lo);
-        FlinkGpu.dictCopyArena(dict, lo, hi - lo, arena);
-        byte[] all = new byte[(int) (hi - lo)];
-        arena.get(all);
+        long nbytes = FlinkGpu.dictRows(dict, keys, count, outBytes, outBytes.capacity(), outOff, outLen);
+        if (nbytes > outBytes.capacity()) {   // too small (nothing was written): grow, once
+            if (nbytes > Integer.MAX_VALUE - 8) {
+                throw new IllegalStateException(
+                        "the key rows of one fired batch take " + nbytes + " bytes: more than a ByteBuffer holds");
+            }
+            outBytes = direct(Math.min(Math.max(nbytes, 2L * outBytes.capacity()), Integer.MAX_VALUE - 8));
+            nbytes = FlinkGpu.dictRows(dict, keys, count, outBytes, outBytes.capacity(), outOff, outLen);
+        }
+        byte[] all = new byte[(int) nbytes];   // (the rows outlive the reused buffer)
+        outBytes.position(0);
+        outBytes.get(all);
         MemorySegment seg = MemorySegmentFactory.wrap(all);
         for (int i = 0; i < count; i++) {
             BinaryRowData r = new BinaryRowData(arity);
-            r.pointTo(seg, (int) (outOff.getLong(8 * i) - lo), outLen.getInt(4 * i));
+            r.pointTo(seg, (int) outOff.getLong(8 * i), outLen.getInt(4 * i));
             out[i] = r;
         }
         return out;

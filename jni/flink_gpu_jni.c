@@ -514,6 +514,25 @@ JNIEXPORT void JNICALL FN(dictLookup)(JNIEnv* env, jclass cls, jlong dp, jobject
     dcheck(env, d, fg_key_dict_lookup(d, FG_HOST, n, i, o, l));
 }
 
+/* long dictRows(long d, ByteBuffer ids, int n, ByteBuffer outBytes, long capBytes, ByteBuffer outOffsets,
+ *               ByteBuffer outLengths) -- the packed bytes the rows take; FG_EFULL is no exception: the
+ * caller sees a result above capBytes (outOffsets / outLengths complete, outBytes untouched), grows
+ * outBytes and calls again. outBytes may be null with capBytes 0 (the sizing call). */
+JNIEXPORT jlong JNICALL FN(dictRows)(JNIEnv* env, jclass cls, jlong dp, jobject ids, jint n, jobject outBytes,
+                                     jlong capBytes, jobject outOffsets, jobject outLengths) {
+    (void)cls;
+    fg_key_dict* d = (fg_key_dict*)(intptr_t)dp;
+    const int64_t* i = (const int64_t*)addr(env, ids);
+    uint8_t* b = (uint8_t*)addr(env, outBytes);
+    int64_t* o = (int64_t*)addr(env, outOffsets);
+    int32_t* l = (int32_t*)addr(env, outLengths);
+    int64_t nbytes = 0;
+    if ((*env)->ExceptionCheck(env)) return 0;
+    const int rc = fg_key_dict_rows(d, FG_HOST, n, i, b, capBytes, o, l, &nbytes);
+    if (rc != FG_EFULL) dcheck(env, d, rc);
+    return nbytes;
+}
+
 /* void dictCopyArena(long d, long begin, long nbytes, ByteBuffer out) */
 JNIEXPORT void JNICALL FN(dictCopyArena)(JNIEnv* env, jclass cls, jlong dp, jlong begin, jlong nbytes, jobject out) {
     (void)cls;
