@@ -132,7 +132,8 @@ EXPORTS = (
     "fg_stream",
     "fg_last_error", "fg_close", "fg_key_groups", "fg_partition_by_owner", "fg_partition_columns_by_owner",
     "fg_abi_version", "fg_key_dict_open", "fg_key_dict_intern", "fg_key_dict_intern_async",
-    "fg_key_dict_intern_wait", "fg_key_dict_lookup", "fg_key_dict_rows", "fg_key_dict_arena",
+    "fg_key_dict_intern_wait", "fg_key_dict_lookup", "fg_key_dict_rows", "fg_partition_keyed_by_owner",
+    "fg_comm_set_key_dicts", "fg_key_dict_arena",
     "fg_key_dict_copy_arena", "fg_key_dict_size", "fg_key_dict_stream", "fg_key_dict_set_timing",
     "fg_key_dict_kernel_stats", "fg_key_dict_last_error", "fg_key_dict_close",
     "fg_binaryrow_hash", "fg_host_register", "fg_host_unregister",
@@ -213,6 +214,11 @@ def load():
     L.fg_key_dict_lookup.argtypes = [P, C.c_int32, C.c_int64, P, P, P]
     L.fg_key_dict_rows.argtypes = [P, C.c_int32, C.c_int64, P, P, C.c_int64, P, P, C.POINTER(C.c_int64)]
     L.fg_key_dict_rows.restype = C.c_int
+    L.fg_partition_keyed_by_owner.argtypes = [P, P, C.c_int64, C.c_int32, P, C.c_int32, P, P, P, P, C.c_int64, P,
+                                              C.POINTER(C.c_int64)]
+    L.fg_partition_keyed_by_owner.restype = C.c_int
+    L.fg_comm_set_key_dicts.argtypes = [P, P, P]
+    L.fg_comm_set_key_dicts.restype = C.c_int
     L.fg_key_dict_arena.argtypes = [P, C.POINTER(P), C.POINTER(C.c_int64)]
     L.fg_key_dict_copy_arena.argtypes = [P, C.c_int64, C.c_int64, P]
     L.fg_key_dict_size.argtypes = [P]

@@ -51,6 +51,15 @@ class Communicator:
     def stream(self) -> int:
         return self._lib.fg_comm_stream(self._h) or 0
 
+    def set_key_dicts(self, local=None, owner=None):
+        """fg_comm_set_key_dicts: the subtask's KeyDictionary pair -- `local` names the keys of the
+        local operator's rows, `owner` those of the global operator's. From now on rounds and
+        exchanges with key_hash=KEYHASH_DICT_ID ship each row's key row and merge under ids of
+        `owner`. Both None detaches. The caller's operator lock covers its own use of the two."""
+        self._check(self._lib.fg_comm_set_key_dicts(self._h, local._h if local is not None else None,
+                                                    owner._h if owner is not None else None))
+        self._key_dicts = (local, owner)   # kept alive while attached
+
     def exchange_columns(self, cols, key_hash=L.KEYHASH_BINARYROW_BIGINT, max_parallelism=128, watermark=0,
                          stream=None):
         """int64 device tensors (cols[0] = key) -> (received column tensors on the device -- views of

@@ -11,6 +11,11 @@
 // one host read of the counts (the receive sizes), then grouped ncclSend / ncclRecv of each
 // column's per-peer runs straight from the partition buffers (no packing copy).
 //
+// Keys that are ids of per-rank key dictionaries (FG_KEYHASH_DICT_ID after fg_comm_set_key_dicts)
+// cross as key rows: each partial row travels with its key row's bytes, as the reference ships the
+// key BinaryRowData with every partial row (LocalAggCombiner.java:100-106), and the owner interns
+// them into its own dictionary. The round stays stateless: a failed one needs no repair.
+//
 // The communicator is bootstrapped the way the JobManager would: one rank makes an
 // ncclUniqueId (fg_comm_unique_id), the 128 bytes are distributed with the deployment, every
 // rank calls fg_comm_open(device, world, rank, id).
@@ -26,6 +31,7 @@
 
 #include "../../include/flinkgpu.h"
 #include "fg_kernels.h"
+#include "fg_keydict.h"
 
 using namespace fg;
 
@@ -57,12 +63,16 @@ struct Buf {
     T* as() const { return static_cast<T*>(p); }
 };
 
-// per peer: {rows for it, this rank's watermark, its epoch, its columns << 1 | its status}. The partition's counts
+// Meta words per peer, the same count in every round, keyed or not.
+constexpr int kMeta = 6;
+
+// per peer: {rows for it, this rank's watermark, its epoch, its columns << 1 | its status, the key
+// bytes for it (keyed rounds: the rows' key rows travel with them), keyed}. The partition's counts
 // must add up to the rows handed in; a rank whose round failed (or whose counts do not) sends zero
 // rows and status 1, so every rank learns of it from the one all-to-all and the round ends on all
 // of them together instead of leaving the peers blocked in the data collective
-__global__ void k_comm_meta(const int64_t* counts, int32_t world, int64_t n, int64_t wm, int64_t epoch,
-                            int32_t status, int32_t ncols, int64_t* meta) {
+__global__ void k_comm_meta(const int64_t* counts, const int64_t* byte_counts, int32_t keyed, int32_t world, int64_t n,
+                            int64_t wm, int64_t epoch, int32_t status, int32_t ncols, int64_t* meta) {
     __shared__ int s_ok;
     const int i = (int)threadIdx.x;
     if (i == 0) {
@@ -72,10 +82,12 @@ __global__ void k_comm_meta(const int64_t* counts, int32_t world, int64_t n, int
     }
     __syncthreads();
     if (i < world) {
-        meta[4 * i] = s_ok && counts ? counts[i] : 0;
-        meta[4 * i + 1] = wm;
-        meta[4 * i + 2] = epoch;
-        meta[4 * i + 3] = (int64_t)ncols << 1 | (s_ok ? 0 : 1);   // (the columns its rows carry)
+        meta[kMeta * i] = s_ok && counts ? counts[i] : 0;
+        meta[kMeta * i + 1] = wm;
+        meta[kMeta * i + 2] = epoch;
+        meta[kMeta * i + 3] = (int64_t)ncols << 1 | (s_ok ? 0 : 1);   // (the columns its rows carry)
+        meta[kMeta * i + 4] = s_ok && byte_counts ? byte_counts[i] : 0;
+        meta[kMeta * i + 5] = keyed;   // (the same word to every peer: every rank sees every rank's flag)
     }
 }
 
@@ -89,7 +101,14 @@ struct fg_comm {
     Buf part[kMaxOwnerCols], recv[kMaxOwnerCols];
     Buf scratch, counts, meta_send, meta_recv;
     int64_t sent_total = 0;      // bytes sent to other ranks, all exchanges
-    int64_t* h_meta = nullptr;   // pinned: [world][4] sent, then [world][4] received
+    int64_t* h_meta = nullptr;   // pinned: [world][kMeta] sent, then [world][kMeta] received
+    // keyed rounds (fg_comm_set_key_dicts): the grouped rows' key row lengths and bytes, the key
+    // bytes per owner; what was received of them, and the ids global_keys gives the received rows
+    fg_key_dict *local_keys = nullptr, *global_keys = nullptr;
+    Buf key_len, key_bytes, byte_counts, recv_key_len, recv_key_bytes, recv_ids;
+    bool keyed = false;          // the round prepared ships key rows
+    bool recv_keyed = false;     // ... and so did the last collective
+    int64_t recv_key_nbytes = 0;
     std::string err;
     // the round prepared by fg_comm_round_begin (or by the one-call exchanges)
     bool pending = false;
@@ -164,7 +183,7 @@ int fg_comm_open(int32_t device_id, int32_t world, int32_t rank, const uint8_t* 
     if (hipEventCreateWithFlags(&c->ev_in, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_out, hipEventDisableTiming) != hipSuccess)
         return bail("hipEventCreate");
-    if (hipHostMalloc((void**)&c->h_meta, sizeof(int64_t) * 8 * (size_t)world, hipHostMallocDefault) != hipSuccess)
+    if (hipHostMalloc((void**)&c->h_meta, sizeof(int64_t) * 2 * kMeta * (size_t)world, hipHostMallocDefault) != hipSuccess)
         return bail("hipHostMalloc");
     ncclUniqueId u;
     std::memcpy(&u, id, FG_COMM_ID_BYTES);
@@ -174,6 +193,24 @@ int fg_comm_open(int32_t device_id, int32_t world, int32_t rank, const uint8_t* 
         return bail(ncclGetErrorString(r));
     }
     *out = c;
+    return FG_OK;
+}
+
+int fg_comm_set_key_dicts(fg_comm* c, fg_key_dict* local_keys, fg_key_dict* global_keys) {
+    if (!c) return FG_EINVAL;
+    if (c->pending || c->recv_ready) return c->fail(FG_ESTATE, "fg_comm_set_key_dicts: a round is under way");
+    if ((local_keys == nullptr) != (global_keys == nullptr))
+        return c->fail(FG_EINVAL, "fg_comm_set_key_dicts: both dictionaries, or both NULL");
+    if (local_keys) {
+        if (keydict_max_parallelism(local_keys) != keydict_max_parallelism(global_keys))
+            return c->fail(FG_EINVAL, "fg_comm_set_key_dicts: the dictionaries' max parallelism differs (%d, %d)",
+                           keydict_max_parallelism(local_keys), keydict_max_parallelism(global_keys));
+        if (keydict_device(local_keys) != c->device || keydict_device(global_keys) != c->device)
+            return c->fail(FG_EINVAL, "fg_comm_set_key_dicts: a dictionary is not on the communicator's device %d",
+                           c->device);
+    }
+    c->local_keys = local_keys;
+    c->global_keys = global_keys;
     return FG_OK;
 }
 
@@ -201,7 +238,8 @@ void fg_comm_close(fg_comm* c) {
 // the producer's later work ordered after the partition (the columns may then be reused). status != 0
 // (this rank failed before the round): zero rows, the failure flag for the peers.
 static int round_prepare(fg_comm* c, hipStream_t producer, int64_t n, int32_t ncols, const int64_t* const* cols,
-                         int32_t key_hash, int32_t max_parallelism, int64_t watermark, int64_t epoch, int status) {
+                         int32_t key_hash, int32_t max_parallelism, int64_t watermark, int64_t epoch, int status,
+                         bool partials = true) {
     const int W = c->world;
     c->pending = true;
     c->recv_ready = false;
@@ -209,13 +247,47 @@ static int round_prepare(fg_comm* c, hipStream_t producer, int64_t n, int32_t nc
     c->ncols = ncols;
     COMM_HIP(c, hipSetDevice(c->device));
     COMM_HIP(c, c->counts.ensure(sizeof(int64_t) * W));
-    COMM_HIP(c, c->meta_send.ensure(sizeof(int64_t) * 4 * W));
-    COMM_HIP(c, c->meta_recv.ensure(sizeof(int64_t) * 4 * W));
+    COMM_HIP(c, c->byte_counts.ensure(sizeof(int64_t) * W));
+    COMM_HIP(c, c->meta_send.ensure(sizeof(int64_t) * kMeta * W));
+    COMM_HIP(c, c->meta_recv.ensure(sizeof(int64_t) * kMeta * W));
+    c->keyed = partials && c->local_keys && key_hash == FG_KEYHASH_DICT_ID;   // (fg_comm_exchange_columns moves ids as they are)
     if (producer) {   // the producer's work (the columns) before ours
         COMM_HIP(c, hipEventRecord(c->ev_in, producer));
         COMM_HIP(c, hipStreamWaitEvent(c->stream, c->ev_in, 0));
     }
-    if (c->n > 0) {
+    if (c->keyed && c->n > 0) {
+        // The rows and their key rows, grouped by owner (fg_partition_keyed_by_owner into our buffers;
+        // complete on return: a later intern may move the local dictionary's arena). A failure here is
+        // this rank's failed round: it still writes its meta words and takes part.
+        int64_t* outs[kMaxOwnerCols] = {};
+        for (int j = 0; j < ncols; j++) {
+            COMM_HIP(c, c->part[j].ensure(sizeof(int64_t) * (size_t)n));
+            outs[j] = c->part[j].as<int64_t>();
+        }
+        COMM_HIP(c, c->key_len.ensure(sizeof(int32_t) * (size_t)n));
+        auto exact = [](void* ctx, int64_t nbytes) -> uint8_t* {   // (sized after the one host read)
+            Buf* b = static_cast<Buf*>(ctx);
+            return b->ensure((size_t)nbytes) == hipSuccess ? b->as<uint8_t>() : nullptr;
+        };
+        int64_t nbytes = 0;
+        int rc = FG_EINVAL;
+        if (max_parallelism != keydict_max_parallelism(c->local_keys)) {
+            c->err_begin = "fg_comm keyed round: max_parallelism " + std::to_string(max_parallelism) +
+                           " is not the key dictionaries' " + std::to_string(keydict_max_parallelism(c->local_keys));
+        } else {
+            rc = keydict_partition_keyed(c->local_keys, c->stream, n, ncols, cols, W, outs, c->counts.as<int64_t>(),
+                                         c->key_len.as<int32_t>(), exact, &c->key_bytes, c->byte_counts.as<int64_t>(),
+                                         &nbytes);
+            if (rc) c->err_begin = std::string("fg_comm keyed round: ") + fg_key_dict_last_error(c->local_keys);
+        }
+        if (rc) {
+            c->rc_begin = rc;
+            status = 1;
+            c->n = 0;
+            COMM_HIP(c, hipMemsetAsync(c->counts.p, 0, sizeof(int64_t) * W, c->stream));
+            COMM_HIP(c, hipMemsetAsync(c->byte_counts.p, 0, sizeof(int64_t) * W, c->stream));
+        }
+    } else if (c->n > 0) {
         OwnerCols oc{};
         oc.ncols = ncols;
         for (int j = 0; j < ncols; j++) {
@@ -230,8 +302,9 @@ static int round_prepare(fg_comm* c, hipStream_t producer, int64_t n, int32_t nc
     } else {
         COMM_HIP(c, hipMemsetAsync(c->counts.p, 0, sizeof(int64_t) * W, c->stream));
     }
-    fg_launch(k_comm_meta, dim3(1), dim3(1024), 0, c->stream, (const int64_t*)c->counts.as<int64_t>(), W, c->n,
-              watermark, epoch, status, ncols, c->meta_send.as<int64_t>());
+    fg_launch(k_comm_meta, dim3(1), dim3(1024), 0, c->stream, (const int64_t*)c->counts.as<int64_t>(),
+              c->keyed && c->n > 0 ? (const int64_t*)c->byte_counts.as<int64_t>() : (const int64_t*)nullptr,
+              c->keyed ? 1 : 0, W, c->n, watermark, epoch, status, ncols, c->meta_send.as<int64_t>());
     COMM_HIP(c, hipGetLastError());
     if (producer && c->n > 0) {   // (the producer may overwrite the columns once the partition has read them)
         COMM_HIP(c, hipEventRecord(c->ev_out, c->stream));
@@ -247,30 +320,38 @@ static int round_collective(fg_comm* c, fg_exchanged* x, fg_round* r) {
     if (!c->pending) return c->fail(FG_ESTATE, "fg_comm_round_exchange: no round begun");
     c->pending = false;
     const int W = c->world;
-    COMM_NCCL(c, ncclAllToAll(c->meta_send.p, c->meta_recv.p, 4, ncclInt64, c->comm, c->stream));
-    COMM_HIP(c, hipMemcpyAsync(c->h_meta, c->meta_send.p, sizeof(int64_t) * 4 * W, hipMemcpyDeviceToHost, c->stream));
-    COMM_HIP(c, hipMemcpyAsync(c->h_meta + 4 * W, c->meta_recv.p, sizeof(int64_t) * 4 * W, hipMemcpyDeviceToHost,
+    COMM_NCCL(c, ncclAllToAll(c->meta_send.p, c->meta_recv.p, kMeta, ncclInt64, c->comm, c->stream));
+    COMM_HIP(c, hipMemcpyAsync(c->h_meta, c->meta_send.p, sizeof(int64_t) * kMeta * W, hipMemcpyDeviceToHost, c->stream));
+    COMM_HIP(c, hipMemcpyAsync(c->h_meta + kMeta * W, c->meta_recv.p, sizeof(int64_t) * kMeta * W, hipMemcpyDeviceToHost,
                                c->stream));
     COMM_HIP(c, hipStreamSynchronize(c->stream));
     const int64_t* ms = c->h_meta;
-    const int64_t* mr = c->h_meta + 4 * W;
+    const int64_t* mr = c->h_meta + kMeta * W;
     std::vector<int64_t> soff(W + 1, 0), roff(W + 1, 0);
+    std::vector<int64_t> ksoff(W + 1, 0), kroff(W + 1, 0);   // key bytes (keyed rounds; zeros otherwise)
     int64_t wmin = INT64_MAX, emin = INT64_MAX;
     int failed = -1, rcols = 0;
     bool mixed = false;   // peers sending rows of different column counts (never, for one operator)
+    bool unlike = false;  // ranks that disagree about shipping key rows (some attached dictionaries, some not)
+    const bool keyed = mr[5] != 0;
     for (int p = 0; p < W; p++) {
-        soff[p + 1] = soff[p] + ms[4 * p];
-        roff[p + 1] = roff[p] + mr[4 * p];
-        wmin = std::min(wmin, mr[4 * p + 1]);
-        emin = std::min(emin, mr[4 * p + 2]);
-        if ((mr[4 * p + 3] & 1) != 0 && failed < 0) failed = p;
-        if (mr[4 * p] > 0) {
-            const int pc = (int)(mr[4 * p + 3] >> 1);
+        soff[p + 1] = soff[p] + ms[kMeta * p];
+        roff[p + 1] = roff[p] + mr[kMeta * p];
+        ksoff[p + 1] = ksoff[p] + ms[kMeta * p + 4];
+        kroff[p + 1] = kroff[p] + mr[kMeta * p + 4];
+        wmin = std::min(wmin, mr[kMeta * p + 1]);
+        emin = std::min(emin, mr[kMeta * p + 2]);
+        if ((mr[kMeta * p + 3] & 1) != 0 && failed < 0) failed = p;
+        unlike = unlike || (mr[kMeta * p + 5] != 0) != keyed;
+        if (mr[kMeta * p] > 0) {
+            const int pc = (int)(mr[kMeta * p + 3] >> 1);
             mixed = mixed || (rcols != 0 && pc != rcols) || pc < 1 || pc > kMaxOwnerCols;
             rcols = pc;
         }
     }
-    if (mixed && failed < 0) failed = W;   // (every rank sees every peer's count: all decide alike)
+    // (every rank sees every peer's column count and keyed flag: all decide alike, before any
+    // collective whose sizes would not match)
+    if ((mixed || unlike) && failed < 0) failed = W;
     if (r) {
         std::memset(r, 0, sizeof *r);
         r->min_watermark = wmin;
@@ -279,6 +360,9 @@ static int round_collective(fg_comm* c, fg_exchanged* x, fg_round* r) {
     }
     if (failed >= 0) {
         if (c->rc_begin != FG_OK) return c->fail(FG_EDEVICE, "this rank's round failed: %s", c->err_begin.c_str());
+        if (failed == W && !mixed)
+            return c->fail(FG_EDEVICE, "fg_comm round: the ranks disagree about shipping key rows (fg_comm_set_key_dicts "
+                                       "on every rank of a job, or on none)");
         if (failed == W) return c->fail(FG_EDEVICE, "fg_comm round: peers sent rows of different column counts");
         if (failed == c->rank)   // (the counts of the partition did not add up to the rows)
             return c->fail(FG_EDEVICE, "fg_comm round: the owner partition counted %lld of %lld rows",
@@ -289,20 +373,41 @@ static int round_collective(fg_comm* c, fg_exchanged* x, fg_round* r) {
     if (rcols == 0) rcols = c->ncols;
     for (int j = 0; j < rcols; j++)
         COMM_HIP(c, c->recv[j].ensure(sizeof(int64_t) * (size_t)std::max<int64_t>(total, 1)));
+    if (keyed) {
+        COMM_HIP(c, c->recv_key_len.ensure(sizeof(int32_t) * (size_t)std::max<int64_t>(total, 1)));
+        COMM_HIP(c, c->recv_key_bytes.ensure((size_t)std::max<int64_t>(kroff[W], 8)));
+    }
     if (total > 0 || c->n > 0) {
         COMM_NCCL(c, ncclGroupStart());
         for (int p = 0; p < W; p++) {
-            for (int j = 0; j < c->ncols && ms[4 * p] > 0; j++)
-                COMM_NCCL(c, ncclSend(c->part[j].as<int64_t>() + soff[p], (size_t)ms[4 * p], ncclInt64, p, c->comm,
+            for (int j = 0; j < c->ncols && ms[kMeta * p] > 0; j++)
+                COMM_NCCL(c, ncclSend(c->part[j].as<int64_t>() + soff[p], (size_t)ms[kMeta * p], ncclInt64, p, c->comm,
                                       c->stream));
-            for (int j = 0; j < rcols && mr[4 * p] > 0; j++)
-                COMM_NCCL(c, ncclRecv(c->recv[j].as<int64_t>() + roff[p], (size_t)mr[4 * p], ncclInt64, p, c->comm,
+            for (int j = 0; j < rcols && mr[kMeta * p] > 0; j++)
+                COMM_NCCL(c, ncclRecv(c->recv[j].as<int64_t>() + roff[p], (size_t)mr[kMeta * p], ncclInt64, p, c->comm,
                                       c->stream));
+            if (!keyed) continue;
+            // the rows' key row lengths (4 B per row) and their bytes: per-peer runs, in the rows' order
+            if (ms[kMeta * p] > 0)
+                COMM_NCCL(c, ncclSend(c->key_len.as<int32_t>() + soff[p], (size_t)ms[kMeta * p], ncclInt32, p, c->comm,
+                                      c->stream));
+            if (mr[kMeta * p] > 0)
+                COMM_NCCL(c, ncclRecv(c->recv_key_len.as<int32_t>() + roff[p], (size_t)mr[kMeta * p], ncclInt32, p,
+                                      c->comm, c->stream));
+            if (ms[kMeta * p + 4] > 0)
+                COMM_NCCL(c, ncclSend(c->key_bytes.as<uint8_t>() + ksoff[p], (size_t)ms[kMeta * p + 4], ncclUint8, p,
+                                      c->comm, c->stream));
+            if (mr[kMeta * p + 4] > 0)
+                COMM_NCCL(c, ncclRecv(c->recv_key_bytes.as<uint8_t>() + kroff[p], (size_t)mr[kMeta * p + 4], ncclUint8,
+                                      p, c->comm, c->stream));
         }
         COMM_NCCL(c, ncclGroupEnd());
     }
     COMM_HIP(c, hipEventRecord(c->ev_out, c->stream));
-    const int64_t sent = 8 * (int64_t)c->ncols * (c->n - ms[4 * c->rank]);
+    int64_t sent = 8 * (int64_t)c->ncols * (c->n - ms[kMeta * c->rank]);
+    if (keyed) sent += 4 * (c->n - ms[kMeta * c->rank]) + (ksoff[W] - ms[kMeta * c->rank + 4]);
+    c->recv_keyed = keyed;
+    c->recv_key_nbytes = kroff[W];
     c->sent_total += sent;
     c->recv_n = total;
     c->recv_ncols = rcols;
@@ -342,7 +447,7 @@ int fg_comm_exchange_columns(fg_comm* c, void* stream, int64_t n, int32_t ncols,
         }
     // (a rank with bad arguments still takes part: its peers learn of the failure from the meta words)
     if (int rc = round_prepare(c, static_cast<hipStream_t>(stream), n, status ? 1 : ncols, cols, key_hash,
-                               std::max(max_parallelism, c->world), watermark, 0, status))
+                               std::max(max_parallelism, c->world), watermark, 0, status, false))
         return rc;
     const int rc = round_collective(c, out, nullptr);
     if (status) return c->fail(c->rc_begin, "%s", c->err_begin.c_str());
@@ -364,6 +469,17 @@ static int round_merge(fg_comm* c, fg_handle* global) {
     p.n = c->recv_n;
     p.location = FG_DEVICE;
     p.key = c->recv[0].as<int64_t>();
+    if (c->recv_keyed) {
+        // the received key rows interned into the owner's dictionary (its stream waits for the
+        // collective; complete on return): their ids are the key column of the merge
+        if (!c->global_keys) return c->fail(FG_ESTATE, "fg_comm_round_end: the key dictionaries were detached mid-round");
+        COMM_HIP(c, c->recv_ids.ensure(sizeof(int64_t) * (size_t)c->recv_n));
+        if (int rc = keydict_intern_packed(c->global_keys, c->ev_out, c->recv_n, c->recv_key_len.as<int32_t>(),
+                                           c->recv_key_bytes.as<uint8_t>(), c->recv_key_nbytes,
+                                           c->recv_ids.as<int64_t>()))
+            return c->fail(rc, "fg_comm_round_end: %s", fg_key_dict_last_error(c->global_keys));
+        p.key = c->recv_ids.as<int64_t>();
+    }
     p.slice_end = c->recv[1].as<int64_t>();
     p.cnt_star = c->recv[2].as<int64_t>();
     p.cnt_val = c->recv[3].as<int64_t>();

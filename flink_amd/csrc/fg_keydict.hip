@@ -28,6 +28,10 @@
 // exact whatever the hash. The way out is fg_key_dict_rows: the packed key rows of ids, gathered
 // by k_rows_* (lengths and a 64-bit scan for the offsets, one host read, then a copy balanced by
 // bytes) -- fired rows, checkpoints and a rescale's re-intern copy those rows, never an arena range.
+// The keyed two-phase edge uses both ends: fg_partition_keyed_by_owner groups rows keyed by ids by
+// owner and gathers their key rows in the grouped order (the same k_rows_* pipeline on the caller's
+// stream, k_owner_byte_counts for the bytes per owner), and keydict_intern_packed (fg_keydict.h)
+// checks and scans the lengths an owner received (k_recv_lengths) and interns the rows.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -41,6 +45,8 @@
 #include <vector>
 
 #include "../../include/flinkgpu.h"
+#include "fg_kernels.h"
+#include "fg_keydict.h"
 #include "fg_window.h"
 
 using namespace fg;
@@ -608,6 +614,49 @@ __global__ __launch_bounds__(kDictThreads) void k_rows_copy(DictDev d, int64_t n
     }
 }
 
+// ---- the keyed edge (fg_partition_keyed_by_owner, keydict_intern_packed) ----
+//
+// Sender: the rows are grouped by owner (counts[par]) and their key rows packed in the grouped
+// order, so owner p's key bytes are the offsets at its run's two boundaries: off[end_p] -
+// off[begin_p], the boundaries being the exclusive scan of counts. One workgroup.
+__global__ __launch_bounds__(kDictThreads) void k_owner_byte_counts(const int64_t* counts, int32_t par, const int64_t* off,
+                                                                    int64_t n, int64_t* byte_counts) {
+    __shared__ uint64_t s_wave[kDictThreads / 64];
+    uint64_t carry = 0;   // (the same in every thread)
+    for (int32_t p0 = 0; p0 < par; p0 += kDictThreads) {
+        const int32_t p = p0 + (int32_t)threadIdx.x;
+        const uint64_t c = p < par && counts[p] > 0 ? (uint64_t)counts[p] : 0ull;
+        uint64_t total;
+        const uint64_t b = carry + block_exclusive_scan_u64(c, s_wave, &total);
+        carry += total;
+        if (p < par) {   // (clamped: counts that do not add up to n never index past off[n])
+            const uint64_t lo = b < (uint64_t)n ? b : (uint64_t)n;
+            const uint64_t hi = b + c < (uint64_t)n ? b + c : (uint64_t)n;
+            byte_counts[p] = off[hi] - off[lo];
+        }
+    }
+}
+
+// Receiver: the lengths as they came off the wire. A length that is negative, not a multiple of 4
+// or >= 2^24 is counted (rc->bad, rc->bad_first) and taken as 0; each block's padded bytes go to
+// sums (k_rows_scan_sums and k_rows_offsets then give the offsets). No key byte is read here.
+__global__ __launch_bounds__(kDictThreads) void k_recv_lengths(int64_t n, const int32_t* len_in, uint64_t* sums,
+                                                               RowsCtr* rc) {
+    __shared__ uint64_t s_wave[kDictThreads / 64];
+    const int64_t i = (int64_t)blockIdx.x * kRowsBlock + threadIdx.x;
+    const bool valid = i < n;
+    const int32_t len = valid ? len_in[i] : 0;
+    const bool ok = len >= 0 && len < (1 << 24) && (len & 3) == 0;
+    const unsigned long long badm = __ballot(valid && !ok);
+    if (badm && (threadIdx.x & 63) == 0) {
+        atomicAdd(&rc->bad, (unsigned long long)__popcll(badm));
+        atomicMin(&rc->bad_first, (unsigned long long)(i - (threadIdx.x & 63) + __ffsll((long long)badm) - 1));
+    }
+    uint64_t total;
+    (void)block_exclusive_scan_u64(ok ? padded8(len) : 0ull, s_wave, &total);
+    if (threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+
 __global__ __launch_bounds__(kDictThreads) void k_slots_clear(Slot* p, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * kDictThreads + threadIdx.x;
     if (i < n) {
@@ -667,6 +716,8 @@ struct fg_key_dict {
     // fg_key_dict_rows: its counters (RowsCtr), the block sums, and for FG_HOST callers the device
     // ids, lengths, offsets and packed bytes; grown on demand and reused across calls
     Buf rows_ctr, rows_sums, rows_ids, rows_len, rows_off, rows_bytes;
+    Buf part_scratch;                // fg_partition_keyed_by_owner: the owner partition's histogram and offsets
+    hipEvent_t ev_order = nullptr;   // ... and the event that orders a caller's stream after the dictionary's
     std::unordered_map<std::string, int64_t> side;   // rows whose tag another row holds
     std::string err;
     // kernel timing (fg_key_dict_set_timing): HIP events around each chunk's probe and its
@@ -797,6 +848,40 @@ int resolve_collisions(fg_key_dict* d, bool host, int64_t n, const uint8_t* byte
     DCHK(d, hipMemcpy(ids, hid.data(), 8 * (size_t)n, hipMemcpyHostToDevice));
     const unsigned long long c2[3] = {(unsigned long long)d->nids, (unsigned long long)d->arena_used, 0ull};
     DCHK(d, hipMemcpy(d->counters.p, c2, sizeof c2, hipMemcpyHostToDevice));
+    return FG_OK;
+}
+
+// The rows pipeline of fg_key_dict_rows and fg_partition_keyed_by_owner, on stream s (the
+// dictionary's, or a caller's ordered after it) over device ids. Stage 1: lengths[n] (-1 for an
+// unknown id), offsets[n + 1] and the call's RowsCtr (d->rows_ctr, for the one host read).
+int rows_lengths_offsets(fg_key_dict* d, hipStream_t s, int64_t n, const int64_t* ids, int32_t* len_out,
+                         int64_t* off_out) {
+    const int64_t nb = (n + kRowsBlock - 1) / kRowsBlock;
+    DCHK(d, d->rows_ctr.ensure(sizeof(RowsCtr), s));
+    DCHK(d, d->rows_sums.ensure(8 * (size_t)nb, s));
+    RowsCtr* rc = d->rows_ctr.as<RowsCtr>();
+    uint64_t* sums = d->rows_sums.as<uint64_t>();
+    DCHK(d, hipMemsetAsync(rc, 0, offsetof(RowsCtr, bad_first), s));
+    DCHK(d, hipMemsetAsync(&rc->bad_first, 0xff, 8, s));
+    if (d->timing) DCHK(d, hipEventRecord(d->ev[3], s));
+    hipLaunchKernelGGL(k_rows_lengths, dim3((unsigned)nb), dim3(kDictThreads), 0, s, d->dev(), d->nids, n, ids, len_out,
+                       sums, rc);
+    hipLaunchKernelGGL(k_rows_scan_sums, dim3(1), dim3(kDictThreads), 0, s, sums, nb, rc, off_out, n);
+    hipLaunchKernelGGL(k_rows_offsets, dim3((unsigned)nb), dim3(kDictThreads), 0, s, n, len_out, sums, off_out);
+    if (d->timing) DCHK(d, hipEventRecord(d->ev[4], s));
+    DCHK(d, hipGetLastError());
+    return FG_OK;
+}
+
+// Stage 2, the copy: only after the host has seen every id good and `total` within the buffer.
+int rows_copy(fg_key_dict* d, hipStream_t s, int64_t n, const int64_t* ids, const int64_t* off, uint8_t* out,
+              int64_t total) {
+    const int64_t nb = (n + kRowsBlock - 1) / kRowsBlock;
+    if (d->timing) DCHK(d, hipEventRecord(d->ev[5], s));
+    hipLaunchKernelGGL(k_rows_copy, dim3((unsigned)nb), dim3(kDictThreads), 0, s, d->dev(), d->nids, n, ids, off,
+                       reinterpret_cast<uint64_t*>(out), total >> 3);
+    if (d->timing) DCHK(d, hipEventRecord(d->ev[6], s));
+    DCHK(d, hipGetLastError());
     return FG_OK;
 }
 
@@ -1081,9 +1166,6 @@ int fg_key_dict_rows(fg_key_dict* d, int32_t location, int64_t n, const int64_t*
     }
     if (hipSetDevice(d->device) != hipSuccess) return d->fail(FG_EDEVICE, "hipSetDevice failed");
     hipStream_t s = d->stream;
-    const int64_t nb = (n + kRowsBlock - 1) / kRowsBlock;
-    DCHK(d, d->rows_ctr.ensure(sizeof(RowsCtr), s));
-    DCHK(d, d->rows_sums.ensure(8 * (size_t)nb, s));
     const int64_t* di = ids;
     int64_t* doff = out_offsets;
     int32_t* dlen = out_lengths;
@@ -1097,17 +1179,8 @@ int fg_key_dict_rows(fg_key_dict* d, int32_t location, int64_t n, const int64_t*
         dlen = d->rows_len.as<int32_t>();
     }
     // 1) lengths and offsets; then the one host read of the call: {total, bad ids, lowest bad index}
-    RowsCtr* rc = d->rows_ctr.as<RowsCtr>();
-    uint64_t* sums = d->rows_sums.as<uint64_t>();
-    const DictDev dv = d->dev();
-    DCHK(d, hipMemsetAsync(rc, 0, offsetof(RowsCtr, bad_first), s));
-    DCHK(d, hipMemsetAsync(&rc->bad_first, 0xff, 8, s));
-    if (d->timing) DCHK(d, hipEventRecord(d->ev[3], s));
-    hipLaunchKernelGGL(k_rows_lengths, dim3((unsigned)nb), dim3(kDictThreads), 0, s, dv, d->nids, n, di, dlen, sums, rc);
-    hipLaunchKernelGGL(k_rows_scan_sums, dim3(1), dim3(kDictThreads), 0, s, sums, nb, rc, doff, n);
-    hipLaunchKernelGGL(k_rows_offsets, dim3((unsigned)nb), dim3(kDictThreads), 0, s, n, dlen, sums, doff);
-    if (d->timing) DCHK(d, hipEventRecord(d->ev[4], s));
-    DCHK(d, hipGetLastError());
+    if (int rc1 = rows_lengths_offsets(d, s, n, di, dlen, doff)) return rc1;
+    RowsCtr* rc = d->rows_ctr.as<RowsCtr>();   // (allocated by the stage above)
     RowsCtr hc;
     DCHK(d, hipMemcpyAsync(&hc, rc, sizeof hc, hipMemcpyDeviceToHost, s));
     DCHK(d, hipStreamSynchronize(s));
@@ -1144,11 +1217,7 @@ int fg_key_dict_rows(fg_key_dict* d, int32_t location, int64_t n, const int64_t*
             DCHK(d, d->rows_bytes.ensure((size_t)total, s));
             dbytes = d->rows_bytes.as<uint8_t>();
         }
-        if (d->timing) DCHK(d, hipEventRecord(d->ev[5], s));
-        hipLaunchKernelGGL(k_rows_copy, dim3((unsigned)nb), dim3(kDictThreads), 0, s, dv, d->nids, n, di, doff,
-                           reinterpret_cast<uint64_t*>(dbytes), total >> 3);
-        if (d->timing) DCHK(d, hipEventRecord(d->ev[6], s));
-        DCHK(d, hipGetLastError());
+        if (int rc2 = rows_copy(d, s, n, di, doff, dbytes, total)) return rc2;
         if (host) DCHK(d, hipMemcpyAsync(out_bytes, dbytes, (size_t)total, hipMemcpyDeviceToHost, s));
     }
     DCHK(d, hipStreamSynchronize(s));
@@ -1159,6 +1228,26 @@ int fg_key_dict_rows(fg_key_dict* d, int32_t location, int64_t n, const int64_t*
     }
     timed(ms);
     return FG_OK;
+}
+
+int fg_partition_keyed_by_owner(fg_key_dict* d, void* stream, int64_t n, int32_t ncols, const int64_t* const* cols,
+                                int32_t parallelism, int64_t* const* out_cols, int64_t* counts, int32_t* out_key_lengths,
+                                uint8_t* out_key_bytes, int64_t cap_bytes, int64_t* out_byte_counts, int64_t* out_nbytes) {
+    if (!d) return FG_EINVAL;
+    if (cap_bytes < 0 || (cap_bytes > 0 && !out_key_bytes))
+        return d->fail(FG_EINVAL, "fg_partition_keyed_by_owner: invalid arguments");
+    if ((uintptr_t)out_key_bytes % 8 != 0)
+        return d->fail(FG_EINVAL, "fg_partition_keyed_by_owner: out_key_bytes must be 8-byte aligned");
+    struct Fixed {
+        uint8_t* p;
+        int64_t cap;
+    } fixed{out_key_bytes, cap_bytes};
+    auto take = [](void* ctx, int64_t nbytes) -> uint8_t* {
+        const Fixed* f = static_cast<const Fixed*>(ctx);
+        return nbytes <= f->cap ? f->p : nullptr;
+    };
+    return keydict_partition_keyed(d, static_cast<hipStream_t>(stream), n, ncols, cols, parallelism, out_cols, counts,
+                                   out_key_lengths, take, &fixed, out_byte_counts, out_nbytes);
 }
 
 int fg_key_dict_arena(fg_key_dict* d, const uint8_t** dev_bytes, int64_t* size) {
@@ -1212,6 +1301,7 @@ void fg_key_dict_close(fg_key_dict* d) {
     if (s) (void)hipStreamSynchronize(s);
     for (auto e : d->ev)
         if (e) (void)hipEventDestroy(e);
+    if (d->ev_order) (void)hipEventDestroy(d->ev_order);
     delete d;
     if (s) (void)hipStreamDestroy(s);
 }
@@ -1222,3 +1312,137 @@ int32_t fg_binaryrow_hash(const uint8_t* row, int32_t len) {
 }
 
 }  // extern "C"
+
+namespace fg {
+
+int32_t keydict_max_parallelism(const fg_key_dict* d) { return d ? d->max_p : 0; }
+int32_t keydict_device(const fg_key_dict* d) { return d ? d->device : -1; }
+
+int keydict_partition_keyed(fg_key_dict* d, hipStream_t s, int64_t n, int32_t ncols, const int64_t* const* cols,
+                            int32_t parallelism, int64_t* const* out_cols, int64_t* counts, int32_t* out_key_lengths,
+                            keydict_bytes_fn key_bytes, void* ctx, int64_t* out_byte_counts, int64_t* out_nbytes) {
+    if (!d) return FG_EINVAL;
+    if (n < 0 || n > 0x7fffffff || ncols < 1 || ncols > kMaxOwnerCols || parallelism < 1 ||
+        parallelism > std::min(1024, d->max_p) || !key_bytes)
+        return d->fail(FG_EINVAL, "fg_partition_keyed_by_owner: n in [0, 2^31), 1..8 columns and a parallelism in "
+                                  "[1, min(1024, the dictionary's max parallelism)] expected");
+    bool null_arg = n > 0 && (!cols || !out_cols || !counts || !out_key_lengths || !out_byte_counts || !out_nbytes);
+    for (int j = 0; !null_arg && n > 0 && j < ncols; j++) null_arg = !cols[j] || !out_cols[j];
+    if (null_arg) return d->fail(FG_EINVAL, "fg_partition_keyed_by_owner: a NULL column or output");
+    if (d->pend.active)
+        return d->fail(FG_ESTATE, "fg_partition_keyed_by_owner: an async intern is pending (fg_key_dict_intern_wait)");
+    if (hipSetDevice(d->device) != hipSuccess) return d->fail(FG_EDEVICE, "hipSetDevice failed");
+    if (n == 0) {
+        if (out_nbytes) *out_nbytes = 0;
+        if (counts) DCHK(d, hipMemsetAsync(counts, 0, 8 * (size_t)parallelism, s));
+        if (out_byte_counts) DCHK(d, hipMemsetAsync(out_byte_counts, 0, 8 * (size_t)parallelism, s));
+        DCHK(d, hipStreamSynchronize(s));
+        return FG_OK;
+    }
+    // after everything queued on the dictionary's stream (an intern's writes to the arena)
+    if (s != d->stream) {
+        if (!d->ev_order) DCHK(d, hipEventCreateWithFlags(&d->ev_order, hipEventDisableTiming));
+        DCHK(d, hipEventRecord(d->ev_order, d->stream));
+        DCHK(d, hipStreamWaitEvent(s, d->ev_order, 0));
+    }
+    // 1) the owner partition of the columns (an id carries its key group: FG_KEYHASH_DICT_ID)
+    const size_t words = partition_scratch_words(n, parallelism);
+    DCHK(d, d->part_scratch.ensure(4 * words, s));
+    DCHK(d, d->rows_off.ensure(8 * (size_t)(n + 1), s));
+    OwnerCols oc{};
+    oc.ncols = ncols;
+    for (int j = 0; j < ncols; j++) {
+        oc.in[j] = cols[j];
+        oc.out[j] = out_cols[j];
+    }
+    DCHK(d, launch_partition_cols_by_owner(oc, n, FG_KEYHASH_DICT_ID, d->max_p, parallelism, counts,
+                                           d->part_scratch.as<uint32_t>(), words, s));
+    // 2) the key rows of the grouped ids: lengths, offsets, the bytes per owner; one host read
+    int64_t* off = d->rows_off.as<int64_t>();
+    if (int rc = rows_lengths_offsets(d, s, n, out_cols[0], out_key_lengths, off)) return rc;
+    hipLaunchKernelGGL(k_owner_byte_counts, dim3(1), dim3(kDictThreads), 0, s, (const int64_t*)counts, parallelism,
+                       (const int64_t*)off, n, out_byte_counts);
+    DCHK(d, hipGetLastError());
+    RowsCtr hc;
+    DCHK(d, hipMemcpyAsync(&hc, d->rows_ctr.p, sizeof hc, hipMemcpyDeviceToHost, s));
+    DCHK(d, hipStreamSynchronize(s));
+    float ms = 0.f;
+    if (d->timing) DCHK(d, hipEventElapsedTime(&ms, d->ev[3], d->ev[4]));
+    auto timed = [&](float t) {
+        if (!d->timing) return;
+        d->kstat[2].launches++;
+        d->kstat[2].total_ms += t;
+        d->kstat[2].records += n;
+    };
+    if (hc.bad) {
+        timed(ms);
+        return d->fail(FG_EINVAL, "fg_partition_keyed_by_owner: " + std::to_string(hc.bad) +
+                                      " unknown ids (negative, or not below the dictionary's size); the first at "
+                                      "grouped index " + std::to_string(hc.bad_first));
+    }
+    const int64_t total = (int64_t)hc.total;
+    *out_nbytes = total;
+    if (total > 0) {
+        uint8_t* out = key_bytes(ctx, total);
+        if (!out) {
+            timed(ms);
+            return d->fail(FG_EFULL, "fg_partition_keyed_by_owner: the key rows take " + std::to_string(total) +
+                                         " bytes, more than out_key_bytes holds");
+        }
+        // 3) the copy: every id is good and the buffer holds `total` bytes
+        if (int rc = rows_copy(d, s, n, out_cols[0], off, out, total)) return rc;
+        DCHK(d, hipStreamSynchronize(s));
+        if (d->timing) {
+            float ms2 = 0.f;
+            DCHK(d, hipEventElapsedTime(&ms2, d->ev[5], d->ev[6]));
+            ms += ms2;
+        }
+    }
+    timed(ms);
+    return FG_OK;
+}
+
+int keydict_intern_packed(fg_key_dict* d, hipEvent_t ready, int64_t n, const int32_t* lengths, const uint8_t* bytes,
+                          int64_t nbytes, int64_t* out_ids) {
+    if (!d) return FG_EINVAL;
+    if (n < 0 || n > 0x7fffffff || nbytes < 0 || (n > 0 && (!lengths || !out_ids)) || (nbytes > 0 && !bytes) ||
+        (uintptr_t)bytes % 8 != 0)
+        return d->fail(FG_EINVAL, "key rows received: invalid arguments");
+    if (d->pend.active) return d->fail(FG_ESTATE, "key rows received: an async intern is pending (fg_key_dict_intern_wait)");
+    if (n == 0)
+        return nbytes == 0 ? FG_OK : d->fail(FG_EDEVICE, "key rows received: " + std::to_string(nbytes) + " bytes for no row");
+    if (hipSetDevice(d->device) != hipSuccess) return d->fail(FG_EDEVICE, "hipSetDevice failed");
+    hipStream_t s = d->stream;
+    if (ready) DCHK(d, hipStreamWaitEvent(s, ready, 0));
+    const int64_t nb = (n + kRowsBlock - 1) / kRowsBlock;
+    DCHK(d, d->rows_ctr.ensure(sizeof(RowsCtr), s));
+    DCHK(d, d->rows_sums.ensure(8 * (size_t)nb, s));
+    DCHK(d, d->rows_off.ensure(8 * (size_t)(n + 1), s));
+    RowsCtr* rc = d->rows_ctr.as<RowsCtr>();
+    uint64_t* sums = d->rows_sums.as<uint64_t>();
+    int64_t* off = d->rows_off.as<int64_t>();
+    DCHK(d, hipMemsetAsync(rc, 0, offsetof(RowsCtr, bad_first), s));
+    DCHK(d, hipMemsetAsync(&rc->bad_first, 0xff, 8, s));
+    hipLaunchKernelGGL(k_recv_lengths, dim3((unsigned)nb), dim3(kDictThreads), 0, s, n, lengths, sums, rc);
+    hipLaunchKernelGGL(k_rows_scan_sums, dim3(1), dim3(kDictThreads), 0, s, sums, nb, rc, off, n);
+    hipLaunchKernelGGL(k_rows_offsets, dim3((unsigned)nb), dim3(kDictThreads), 0, s, n, lengths, (const uint64_t*)sums, off);
+    DCHK(d, hipGetLastError());
+    RowsCtr hc;
+    DCHK(d, hipMemcpyAsync(&hc, rc, sizeof hc, hipMemcpyDeviceToHost, s));
+    DCHK(d, hipStreamSynchronize(s));
+    if (hc.bad)
+        return d->fail(FG_EDEVICE, "key rows received: " + std::to_string(hc.bad) +
+                                       " lengths negative, not a multiple of 4 or >= 2^24; the first at row " +
+                                       std::to_string(hc.bad_first));
+    if ((int64_t)hc.total != nbytes)
+        return d->fail(FG_EDEVICE, "key rows received: the lengths add up to " + std::to_string(hc.total) + " bytes, " +
+                                       std::to_string(nbytes) + " were received");
+    if (!bytes) {   // (only empty rows: the intern still wants a buffer to point at)
+        DCHK(d, d->rows_bytes.ensure(8, s));
+        bytes = d->rows_bytes.as<uint8_t>();
+    }
+    if (int rc2 = intern_begin(d, FG_DEVICE, n, bytes, nbytes, off, lengths, out_ids, nullptr)) return rc2;
+    return intern_finish(d);
+}
+
+}  // namespace fg

@@ -115,6 +115,46 @@ def partition_columns_by_owner(cols, parallelism: int, max_parallelism: int = 12
     return outs, counts
 
 
+def partition_keyed_by_owner(cols, key_dict, parallelism: int, stream=None):
+    """fg_partition_keyed_by_owner: int64 device columns keyed by ids of `key_dict` (cols[0] = ids),
+    reordered by destination subtask, with the key rows the owners need. Returns (reordered columns,
+    counts[parallelism], key_lengths int32[n], key_bytes uint8[nbytes], byte_counts[parallelism]):
+    row i's key row lies at the exclusive prefix of the lengths padded to 8, and is the row of
+    outs[0][i]. At most two C calls: a guess of 32 bytes per row, one retry of the whole call at
+    the exact size if the rows take more (FG_EFULL). Unknown ids raise KeyError."""
+    lib = L.load()
+    n = cols[0].numel()
+    dev = cols[0].device
+    k = len(cols)
+    cols = [c.contiguous() for c in cols]
+    outs = [torch.empty_like(c) for c in cols]
+    counts = torch.empty(parallelism, dtype=torch.int64, device=dev)
+    byte_counts = torch.empty(parallelism, dtype=torch.int64, device=dev)
+    lengths = torch.empty(n, dtype=torch.int32, device=dev)
+    ins = (C.c_void_p * k)(*[c.data_ptr() for c in cols])
+    ous = (C.c_void_p * k)(*[o.data_ptr() for o in outs])
+    s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    nbytes = C.c_int64()
+    cap = 32 * n
+    for _ in range(2):
+        buf = torch.empty(max(cap, 8), dtype=torch.uint8, device=dev)
+        rc = lib.fg_partition_keyed_by_owner(key_dict._h, C.c_void_p(s), n, k, ins, parallelism, ous,
+                                             C.c_void_p(counts.data_ptr()), C.c_void_p(lengths.data_ptr()),
+                                             C.c_void_p(buf.data_ptr()), cap, C.c_void_p(byte_counts.data_ptr()),
+                                             C.byref(nbytes))
+        if rc != L.FG_EFULL:
+            break
+        cap = int(nbytes.value)
+    if rc:
+        msg = lib.fg_key_dict_last_error(key_dict._h).decode(errors="replace")
+        if rc == L.FG_EINVAL and "unknown ids" in msg:
+            raise KeyError(msg)
+        if rc == L.FG_EINVAL:
+            raise L.WindowSpecError(msg)
+        raise L.FlinkGpuError(rc, msg)
+    return outs, counts, lengths, buf[:int(nbytes.value)], byte_counts
+
+
 def exchange_partials(cols, group=None, max_parallelism: int = 128, key_hash: int = L.KEYHASH_BINARYROW_BIGINT,
                       via_cpu: bool = False, key_rows=None, watermark=None):
     """Key-group exchange of partial accumulator rows (int64 device columns, key first).

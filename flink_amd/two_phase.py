@@ -34,6 +34,13 @@ Backends of a round: `CapiRounds` (fg_comm_round_begin / _exchange / _end, RCCL 
 `TorchRounds` (torch.distributed: RCCL, or gloo through host memory for tests and rehearsals). The
 subtask's operators are reached through a `pair` object (GpuPair for the HIP operators; tests plug
 the oracle in the same way).
+
+Keys of any type (STRING, composite, NULL): the operators aggregate ids of a key dictionary, and an
+id of the sender's dictionary means nothing on the owner, so in a KEYED round every partial row
+travels with its key row (as LocalAggCombiner ships the key BinaryRowData, LocalAggCombiner.java:
+100-106) and the owner interns it into its own dictionary: `GpuPair(..., key_dicts=(local, owner))`
+with `TorchRounds`, or `Communicator.set_key_dicts(local, owner)` with
+`CapiRounds(comm, key_hash=KEYHASH_DICT_ID)`. The round is stateless: a failed one needs no repair.
 """
 from __future__ import annotations
 
@@ -64,33 +71,68 @@ class Round:
 class GpuPair:
     """The HIP local (FG_FLAG_LOCAL_PARTIALS) and global operators of one subtask."""
 
-    def __init__(self, local, glob, device=None):
+    def __init__(self, local, glob, device=None, key_dicts=None):
+        """key_dicts = (local, owner) KeyDictionary pair when the grouping keys are dictionary ids:
+        the local operator's keys are ids of `local`, the global operator's ids of `owner`."""
         import torch
         self.local, self.glob = local, glob
         self.device = device if device is not None else torch.device("cuda", 0)
+        self.key_dicts = key_dicts
 
     def local_batch(self, key, ts, val):
+        """with key dictionaries `key` may be the records' packed key rows (bytes u8, offsets i64,
+        lengths i32 device tensors): they are interned into the local dictionary here, under the
+        subtask's lock -- the edge thread's rounds use the same dictionary"""
+        if self.key_dicts is not None and isinstance(key, tuple):
+            key = self.key_dicts[0].intern_rows(*key)
         self.local.process_batch(key, ts, val)
 
     def local_watermark(self, wm: int):
         self.local.process_watermarks([int(wm)])
 
     def local_rows(self, mode, world, max_parallelism, key_hash):
-        """the round's local partial rows grouped by owner: (int64 device columns, counts[world])"""
+        """the round's local partial rows grouped by owner: (int64 device columns, counts[world]);
+        with key dictionaries a third value, the grouped rows' key rows (key_lengths int32[n],
+        key_bytes uint8[], byte_counts[world]) of fg_partition_keyed_by_owner (None when idle)"""
         import torch
 
-        from .exchange import device_columns, partition_columns_by_owner
+        from .exchange import device_columns, partition_columns_by_owner, partition_keyed_by_owner
+        keyed = self.key_dicts is not None
         if mode == IDLE:
-            return None, torch.zeros(world, dtype=torch.int64)
+            none = (None, torch.zeros(world, dtype=torch.int64))
+            return none + (None,) if keyed else none
         r = self.local.collect_fired() if mode == FIRED else self.local.flush_partials(device_output=True)
         cols = device_columns(r, aggs=tuple(range(int(r.num_aggs))), device=self.device)
+        if keyed:
+            kd = self.key_dicts[0]
+            if max_parallelism != kd.max_parallelism:
+                raise ValueError(f"max_parallelism {max_parallelism} is not the key dictionaries' {kd.max_parallelism}")
+            # (complete on return: the local operator may fire again, the dictionary intern again)
+            outs, counts, klen, kbytes, bcounts = partition_keyed_by_owner(cols, kd, world)
+            return outs, counts, (klen, kbytes, bcounts)
         outs, counts = partition_columns_by_owner(cols, world, max_parallelism, key_hash)
         torch.cuda.current_stream(self.device).synchronize()   # (the local's rows are read: it may fire again)
         return outs, counts
 
-    def global_add(self, cols):
-        if cols is not None and cols[0].numel():
-            self.glob.process_partials(*cols)
+    def global_add(self, cols, key_rows=None):
+        """the received partial rows merged into the global operator; key_rows = (lengths int32[n],
+        bytes uint8[]) of a keyed round: the rows' key rows, packed back to back and padded to 8,
+        interned into the owner dictionary -- their ids are the key column of the merge"""
+        if cols is None or not cols[0].numel():
+            return
+        if self.key_dicts is not None:
+            import torch
+            if key_rows is None:
+                raise RoundFailed("rows without their key rows reached a subtask with key dictionaries")
+            ln, data = key_rows
+            padded = (ln.to(torch.int64) + 7) & ~7
+            off = torch.cumsum(padded, 0) - padded
+            if int(padded.sum()) != data.numel() or bool(((ln < 0) | (ln % 4 != 0)).any()):
+                raise RoundFailed("the key rows received do not match their lengths")
+            if data.numel() == 0:   # (only empty rows: the intern still wants a buffer to point at)
+                data = data.new_zeros(8)
+            cols = [self.key_dicts[1].intern_rows(data, off, ln)] + list(cols[1:])
+        self.glob.process_partials(*cols)
 
     def global_advance(self, wm: int):
         self.glob.process_watermark(int(wm), device_output=True, wait=False)
@@ -106,14 +148,25 @@ class GpuPair:
         return self.glob.collect_fired(host=True)
 
     def global_snapshot(self):
+        """(image, timer watermark); with key dictionaries a third value, the image's key rows
+        (image_key_rows: the owner ids mean nothing to a restarted subtask's dictionary)"""
         self.glob.prepare_snapshot_pre_barrier()
-        return self.glob.snapshot_state(copy=True)
+        image, twm = self.glob.snapshot_state(copy=True)
+        if self.key_dicts is None:
+            return image, twm
+        return image, twm, image_key_rows(image, self.key_dicts[1])
 
 
 class TorchRounds:
     """A round over torch.distributed (fg_comm_round semantics): ONE all-to-all of (count,
-    watermark, epoch, columns << 1 | failed) per peer, one host read, ONE all-to-all of the rows
-    packed [n, c]. via_cpu stages through host memory (gloo)."""
+    watermark, epoch, columns << 1 | failed, key bytes, keyed) per peer, one host read, ONE
+    all-to-all of the rows packed [n, c]. via_cpu stages through host memory (gloo).
+
+    A pair with key dictionaries (pair.key_dicts) makes the round keyed, as fg_comm_set_key_dicts
+    does on the C side: the rows' key row lengths travel as one more column, their bytes in one more
+    all-to-all (per-peer runs, sized by the meta's key bytes), and the owner interns them
+    (pair.global_add). Every subtask sees every peer's keyed flag, so all decide alike; subtasks
+    that disagree fail the round together."""
 
     def __init__(self, group=None, via_cpu=False, max_parallelism=128, key_hash=L.KEYHASH_BINARYROW_BIGINT):
         import torch.distributed as dist
@@ -123,13 +176,21 @@ class TorchRounds:
         self.rank = dist.get_rank(group)
         self._out = None
         self._recv = None
+        self._kbytes = None
+        self._recv_keys = None
         self.bytes_sent = 0
 
     def begin(self, pair, mode, watermark, epoch):
         import torch
         self._err = None
+        keyed = getattr(pair, "key_dicts", None) is not None
+        krows = None
         try:
-            outs, counts = pair.local_rows(mode, self.world, self.maxp, self.key_hash)
+            res = pair.local_rows(mode, self.world, self.maxp, L.KEYHASH_DICT_ID if keyed else self.key_hash)
+            outs, counts = res[0], res[1]
+            if keyed and outs:
+                klen, self._kbytes, bcounts = krows = res[2]
+                outs = list(outs) + [klen.to(torch.int64)]
         except Exception as e:   # (still takes part in the round: the peers learn of it)
             self._err = e
             outs, counts = None, torch.zeros(self.world, dtype=torch.int64)
@@ -138,11 +199,16 @@ class TorchRounds:
         if outs and int(counts.sum()) != n:
             self._err, outs, counts = RoundFailed("owner partition lost rows"), None, torch.zeros(self.world, dtype=torch.int64)
         fail = 1 if self._err is not None else 0
-        meta = torch.zeros((self.world, 4), dtype=torch.int64)
+        meta = torch.zeros((self.world, 6), dtype=torch.int64)
         meta[:, 0] = counts.cpu() if not fail else 0
         meta[:, 1] = int(watermark)
         meta[:, 2] = int(epoch)
         meta[:, 3] = ncols << 1 | fail
+        if krows is not None and not fail and outs:
+            meta[:, 4] = krows[2].cpu()
+        meta[:, 5] = 1 if keyed else 0   # (the same word to every peer)
+        if fail or not outs:
+            self._kbytes = None
         self._meta = meta if self.via_cpu else meta.to(counts.device)
         self._out = None if fail or not outs else torch.stack(outs, dim=1).contiguous()
 
@@ -160,6 +226,9 @@ class TorchRounds:
         cols = {int(mr[p, 3]) >> 1 for p in range(self.world) if int(mr[p, 0]) > 0}
         if len(cols) > 1:
             raise RoundFailed("subtasks sent rows of different column counts")
+        if len({int(mr[p, 5]) for p in range(self.world)}) > 1:
+            raise RoundFailed("subtasks disagree about shipping key rows (key dictionaries on all, or on none)")
+        keyed = bool(int(mr[0, 5]))
         send, recv = ms[:, 0].tolist(), mr[:, 0].tolist()
         nc = cols.pop() if cols else 0
         self._recv = None
@@ -173,21 +242,44 @@ class TorchRounds:
             dist.all_to_all_single(out, packed, output_split_sizes=recv, input_split_sizes=send, group=self.group)
             self._recv = out
         sent = 8 * nc * (sum(send) - send[self.rank])
+        self._recv_keys = None
+        if keyed and nc:
+            # the key bytes (padded to 8: whole words) as per-peer runs, in the rows' order
+            ksend, krecv = (ms[:, 4] // 8).tolist(), (mr[:, 4] // 8).tolist()
+            kb = self._kbytes if self._kbytes is not None else torch.zeros(0, dtype=torch.uint8)
+            if self.via_cpu:
+                kb = kb.cpu()
+            elif self._kbytes is None:
+                kb = kb.to(self._meta.device)
+            words = kb.contiguous().view(torch.int64) if kb.numel() else torch.zeros(0, dtype=torch.int64, device=kb.device)
+            rwords = torch.empty(sum(krecv), dtype=torch.int64, device=words.device)
+            dist.all_to_all_single(rwords, words, output_split_sizes=krecv, input_split_sizes=ksend, group=self.group)
+            self._recv_keys = rwords.view(torch.uint8) if rwords.numel() else torch.zeros(0, dtype=torch.uint8, device=rwords.device)
+            sent += 8 * (sum(ksend) - ksend[self.rank])
         self.bytes_sent += sent
         return Round(int(mr[:, 1].min()), int(mr[:, 2].min()), sum(send), sum(recv), sent)
 
     def end(self, pair, device=None):
+        import torch
         if self._recv is None or self._recv.shape[0] == 0:
             return
         r = self._recv
         if device is not None and r.device != device:
             r = r.to(device)
-        pair.global_add([c.contiguous() for c in r.unbind(1)])
+        cols = [c.contiguous() for c in r.unbind(1)]
+        if self._recv_keys is None:
+            pair.global_add(cols)
+            return
+        kb = self._recv_keys
+        if device is not None and kb.device != device:
+            kb = kb.to(device)
+        pair.global_add(cols[:-1], (cols[-1].to(torch.int32), kb))
 
 
 class CapiRounds:
     """A round through the C-ABI (fg_comm_round_begin / _exchange / _end over RCCL): the pair's
-    operators are HIP handles (GpuPair)."""
+    operators are HIP handles (GpuPair). Keyed simply by key_hash=KEYHASH_DICT_ID after
+    comm.set_key_dicts(local, owner): the library ships and interns the key rows itself."""
 
     def __init__(self, comm, max_parallelism=128, key_hash=L.KEYHASH_BINARYROW_BIGINT):
         self.comm, self.maxp, self.key_hash = comm, max_parallelism, key_hash
@@ -370,6 +462,30 @@ def restore_union(glob, images, key_hash=None):
     entries of its own key groups (fg_restore_range). Returns the restore's info dict."""
     from . import _lib as L
     return glob.restore_state_range(images, None, L.KEYHASH_BINARYROW_BIGINT if key_hash is None else key_hash)
+
+
+def image_key_rows(image, owner_dict):
+    """At a checkpoint: the key rows of a global image whose key column holds ids of `owner_dict`
+    (KeyDictionary.rows: bytes, offsets[n + 1], lengths) -- stored with the image, since the ids
+    mean nothing to the dictionary of a restarted subtask."""
+    return owner_dict.rows(np.ascontiguousarray(image["key"], dtype=np.int64))
+
+
+def restore_union_dict_ids(glob, sources, owner_dict):
+    """restore_union for images keyed by dictionary ids: sources = [(image, timer watermark, key
+    rows), ...] of every old subtask, the key rows as image_key_rows took them. Each image's key
+    rows are interned into `owner_dict` (the restarted subtask's fresh owner dictionary), the ids
+    it hands out replace the key column, and `glob` keeps the entries of its own key groups
+    (restore_state_range with KEYHASH_DICT_ID: an id carries its key row's key group, the same in
+    every dictionary). Returns the restore's info dict."""
+    from . import _lib as L
+    images = []
+    for img, wm, (buf, off, ln) in sources:
+        if len(buf) == 0:   # (only empty rows, or none: the intern still wants a buffer to point at)
+            buf = np.zeros(8, dtype=np.uint8)
+        ids, _ = owner_dict.intern(packed=(buf, off[:-1], ln), key_groups=False)
+        images.append((dict(img, key=ids), wm))
+    return glob.restore_state_range(images, None, L.KEYHASH_DICT_ID)
 
 
 def keyed_runs(image, index, key_group_range):

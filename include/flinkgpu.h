@@ -529,8 +529,9 @@ int  fg_partition_columns_by_owner(int32_t device_id, void* stream, int64_t n, i
  * (KeyGroupRangeAssignment.java:124-127) with fg_key_hash routing. Per exchange: the rows grouped by
  * owner on the device, ONE all-to-all of (row count, this rank's watermark) per peer, ONE host read
  * of them, grouped send / receive of each column's runs. Collective: every rank calls the same
- * exchanges in the same order (a rank with no rows still calls). Not for per-rank dictionary ids
- * (FG_KEYHASH_DICT_ID of different dictionaries): those ship key rows. */
+ * exchanges in the same order (a rank with no rows still calls). Keys that are ids of per-rank
+ * dictionaries (FG_KEYHASH_DICT_ID) cross as key rows once fg_comm_set_key_dicts (below, after the
+ * key dictionary) has attached the subtask's dictionaries; without it ids move as they are. */
 #define FG_COMM_ID_BYTES 128
 typedef struct fg_comm fg_comm;
 typedef struct fg_exchanged {
@@ -662,6 +663,56 @@ int  fg_key_dict_rows(fg_key_dict* d, int32_t location, int64_t n, const int64_t
                       uint8_t* out_bytes, int64_t cap_bytes,
                       int64_t* out_offsets /* [n + 1] */, int32_t* out_lengths /* [n] */,
                       int64_t* out_nbytes /* always a host pointer */);
+/* fg_partition_columns_by_owner for rows keyed by ids of dictionary d (cols[0] = ids; owner from the key
+ * group an id carries, FG_KEYHASH_DICT_ID, under d's max parallelism), plus what the owner needs to know
+ * the keys: the key rows of the grouped ids, packed back to back in the grouped order, each zero-padded
+ * to 8 bytes (the fg_key_dict_rows layout without its offsets), their lengths, and the key bytes per owner
+ * (ABI 16, added): the sender half of the keyed two-phase edge, at any `parallelism` on one device.
+ * All pointers except out_nbytes are device pointers. The work is queued on `stream` (hipStream_t)
+ * after everything queued on the dictionary's stream, and everything is complete when the call
+ * returns: it reads {total, bad ids} back once, as fg_key_dict_rows does. Row i of the grouped
+ * output has its key row at the exclusive prefix of the padded lengths ((len + 7) & ~7) of rows
+ * 0 .. i-1, and that key row is the row of out_cols[0][i]; the order inside an owner's run is
+ * unspecified (the partition is an atomic counting sort), but the columns, the lengths and the
+ * bytes agree with each other position by position. Returns
+ *   FG_EFULL   *out_nbytes > cap_bytes: out_cols, counts, out_key_lengths, out_byte_counts and
+ *              *out_nbytes are complete, out_key_bytes is untouched. out_key_bytes NULL with
+ *              cap_bytes 0 is the sizing call;
+ *   FG_EINVAL  before any device work: a NULL d; n < 0 or n > 2^31 - 1; ncols outside 1..8;
+ *              parallelism outside 1..min(1024, d's max parallelism); n > 0 with a NULL column or
+ *              output; cap_bytes < 0, or > 0 with a NULL out_key_bytes; a misaligned out_key_bytes;
+ *   FG_EINVAL  after the length pass: an id that is negative or whose ordinal is not below
+ *              fg_key_dict_size -- the message gives how many and the lowest grouped index; no key
+ *              byte is written;
+ *   FG_ESTATE  while an async intern is pending.
+ * n == 0: counts and out_byte_counts are zeroed (where non-NULL) and *out_nbytes = 0. The
+ * dictionary is not modified and stays usable after every error. */
+int  fg_partition_keyed_by_owner(fg_key_dict* d, void* stream, int64_t n, int32_t ncols,
+        const int64_t* const* cols, int32_t parallelism, int64_t* const* out_cols,
+        int64_t* counts            /* device [parallelism] */,
+        int32_t* out_key_lengths   /* device [n], grouped order */,
+        uint8_t* out_key_bytes, int64_t cap_bytes /* device, 8-byte aligned */,
+        int64_t* out_byte_counts   /* device [parallelism]: sum of padded lengths per owner */,
+        int64_t* out_nbytes        /* host */);
+/* The dictionaries of a subtask whose grouping keys are dictionary ids: from now on every exchange
+ * with key_hash == FG_KEYHASH_DICT_ID ships each row's key row and the receiver's key column holds ids
+ * of global_keys. Both NULL detaches. FG_EINVAL: only one NULL, different max parallelism, a device
+ * other than the communicator's. Every rank of a job attaches, or none does (ranks that disagree
+ * fail their round together, fg_round.failed_rank = world).
+ * With dictionaries attached, fg_comm_round_* and fg_comm_exchange_partials / _fired / _flushed
+ * (fg_comm_exchange_columns stays unkeyed): _begin groups the local rows with
+ * fg_partition_keyed_by_owner over local_keys at `world` owners -- max_parallelism must be the
+ * dictionaries'; the gather of the key rows has completed when _begin returns; an unknown id, a
+ * pending async intern or a device error there is this rank's failed round, reported through the
+ * meta words like any other; _exchange moves, with the columns, 4 bytes of length per row and the
+ * key bytes (every row carries its key: the round is stateless, a failed one needs no repair) and
+ * counts them in bytes_sent; _end checks what it received (FG_EDEVICE, nothing interned, for a
+ * length that is negative, not a multiple of 4 or >= 2^24, or lengths that do not add up to the
+ * bytes received), interns it into global_keys and merges the rows under those ids.
+ * A dictionary handle is single-threaded: fg_comm uses local_keys only inside _begin and
+ * global_keys only inside _end (the one-call forms use both), so the lock under which the caller
+ * makes those calls (its operator lock) must also cover its own use of the two dictionaries. */
+int  fg_comm_set_key_dicts(fg_comm* c, fg_key_dict* local_keys, fg_key_dict* global_keys);
 /* The arena (device memory, rows padded to 8 bytes) and its used size; valid until the next intern. */
 int  fg_key_dict_arena(fg_key_dict* d, const uint8_t** dev_bytes, int64_t* size);
 int  fg_key_dict_copy_arena(fg_key_dict* d, int64_t begin, int64_t nbytes, uint8_t* host);

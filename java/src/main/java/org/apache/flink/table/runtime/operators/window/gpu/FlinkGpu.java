@@ -237,6 +237,9 @@ public final class FlinkGpu {
     /** fg_key_hash: a BIGINT key hashed as its BinaryRowData key row (FG_KEYHASH_BINARYROW_BIGINT). */
     public static final int KEYHASH_BINARYROW_BIGINT = 0;
 
+    /** fg_key_hash: an id of a key dictionary, routed by the key group it carries (FG_KEYHASH_DICT_ID). */
+    public static final int KEYHASH_DICT_ID = 2;
+
     /** Bytes of a communicator id (FG_COMM_ID_BYTES). */
     public static final int COMM_ID_BYTES = 128;
 
@@ -279,6 +282,14 @@ public final class FlinkGpu {
 
     /** fg_comm_round_end: the received partial rows merged into the global handle. */
     public static native void commRoundEnd(long comm, long global);
+
+    /**
+     * fg_comm_set_key_dicts: the subtask's key dictionaries (dictOpen handles; 0, 0 detaches). From
+     * now on rounds and exchanges with KEYHASH_DICT_ID ship each partial row's key row and merge
+     * under ids of globalDict. Every subtask of a job attaches, or none. The lock that covers
+     * commRoundBegin / commRoundEnd must also cover the caller's own use of the two dictionaries.
+     */
+    public static native void commSetKeyDicts(long comm, long localDict, long globalDict);
 
     /** fg_comm_bytes_sent. */
     public static native long commBytesSent(long comm);

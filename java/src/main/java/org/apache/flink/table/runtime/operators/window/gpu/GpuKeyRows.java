@@ -9,6 +9,11 @@
  * the GPU gathers exactly those rows, packed in the ids' order, and only they cross to the host
  * (a second call when the reused buffer has to grow) -- never a JNI round trip per row, and no
  * copy of the arena range the ids span.
+ *
+ * The fused two-phase operator holds two of these: the local one (records -> ids of the local
+ * handle) and a dictionary-only one for its global handle, whose ids the keyed RCCL edge hands out
+ * (FlinkGpu.commSetKeyDicts); checkpoint chunks carry the packed key rows of their ids (packed) and
+ * a restore interns them again (internPacked).
  */
 package org.apache.flink.table.runtime.operators.window.gpu;
 
@@ -32,15 +37,27 @@ final class GpuKeyRows implements AutoCloseable {
     private ByteBuffer outBytes, outOff, outLen; // dictRows scratch (reused, grown on demand)
 
     GpuKeyRows(GpuWindowAggSpec spec, int maxParallelism) {
+        this(spec, maxParallelism, true);
+    }
+
+    /** batchBuffers false: the dictionary only (ids come from elsewhere; rows / packed / internPacked) */
+    GpuKeyRows(GpuWindowAggSpec spec, int maxParallelism, boolean batchBuffers) {
         this.bigint = spec.bigintKey;
         this.arity = spec.keyArity;
         this.batch = spec.batchRecords;
         if (!bigint) {
             dict = FlinkGpu.dictOpen(spec.device, maxParallelism, spec.expectedKeys);
-            rows = direct(64L * batch);
-            offsets = direct(8L * batch);
-            lengths = direct(4L * batch);
+            if (batchBuffers) {
+                rows = direct(64L * batch);
+                offsets = direct(8L * batch);
+                lengths = direct(4L * batch);
+            }
         }
+    }
+
+    /** the fg_key_dict handle (0 for a BIGINT key) */
+    long dict() {
+        return dict;
     }
 
     static ByteBuffer direct(long bytes) {
@@ -134,6 +151,56 @@ final class GpuKeyRows implements AutoCloseable {
             out[i] = r;
         }
         return out;
+    }
+
+    /**
+     * the key rows of ids keys[0 .. count) as a checkpoint chunk stores them: count int32 lengths,
+     * then the rows packed back to back, each zero-padded to 8 (one dictRows, a second if the
+     * scratch has to grow)
+     */
+    byte[] packed(ByteBuffer keys, int count) {
+        if (bigint || count == 0) {
+            return new byte[0];
+        }
+        if (outOff == null || outOff.capacity() < 8L * (count + 1)) {
+            outOff = direct(8L * (count + 1));
+            outLen = direct(4L * count);
+        }
+        if (outBytes == null) {
+            outBytes = direct(32L * count);
+        }
+        long nbytes = FlinkGpu.dictRows(dict, keys, count, outBytes, outBytes.capacity(), outOff, outLen);
+        if (nbytes > outBytes.capacity()) {
+            outBytes = direct(Math.min(Math.max(nbytes, 2L * outBytes.capacity()), Integer.MAX_VALUE - 8));
+            nbytes = FlinkGpu.dictRows(dict, keys, count, outBytes, outBytes.capacity(), outOff, outLen);
+        }
+        byte[] out = new byte[4 * count + (int) nbytes];
+        outLen.position(0);
+        outLen.get(out, 0, 4 * count);
+        outBytes.position(0);
+        outBytes.get(out, 4 * count, (int) nbytes);
+        return out;
+    }
+
+    /**
+     * packed()'s layout back into ids: count key rows of lengths[0 .. count) (int32) packed back to
+     * back in rows[0 .. nbytes), each padded to 8, interned into this dictionary; their ids go to
+     * keys[0 .. count)
+     */
+    void internPacked(ByteBuffer rows, long nbytes, ByteBuffer lengths, int count, ByteBuffer keys) {
+        if (bigint || count == 0) {
+            return;
+        }
+        ByteBuffer off = direct(8L * count);
+        long at = 0;
+        for (int i = 0; i < count; i++) {
+            off.putLong(8 * i, at);
+            at += (lengths.getInt(4 * i) + 7) & ~7;
+        }
+        if (at != nbytes) {
+            throw new IllegalStateException("a restored chunk's key rows take " + at + " bytes, it holds " + nbytes);
+        }
+        FlinkGpu.dictIntern(dict, rows, nbytes, off, lengths, count, keys, null);
     }
 
     /** the key rows of the given ids (a restore re-interns the image's rows first) */

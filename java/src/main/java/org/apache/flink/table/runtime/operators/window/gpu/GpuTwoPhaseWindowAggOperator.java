@@ -35,9 +35,18 @@
  * (commOpen blocks until every subtask joined) while the task thread goes on taking records. The
  * coordinator fails the job when a subtask fails (the collectives join every subtask).
  *
- * BIGINT grouping keys (the C-ABI edge moves the keys themselves: per-subtask dictionary ids of
- * other key types mean nothing on another subtask -- the planner keeps the reference's two operators
- * for those). Python mirror: flink_amd/two_phase.py (TwoPhaseSubtask), tested at world size 2.
+ * Grouping keys: BIGINT keys cross the edge as they are. Any other key (STRING, several columns, a
+ * NULL key) is a BinaryRowData key row interned by a key dictionary per handle: the local GpuKeyRows
+ * turns the records' key rows into ids of the local handle (interned in flushBatch under the lock),
+ * and an id of one subtask's dictionary means nothing on another, so the keyed edge
+ * (FlinkGpu.commSetKeyDicts, KEYHASH_DICT_ID) ships every partial row's key row -- as the reference's
+ * LocalAggCombiner emits the key BinaryRowData (LocalAggCombiner.java:100-106) -- and interns it
+ * into the global GpuKeyRows' dictionary inside commRoundEnd; fired rows get their key rows back
+ * from that dictionary. The lock that covers commRoundBegin / commRoundEnd covers every other use
+ * of the two dictionaries. The union-state chunks of such an operator carry each row's key row
+ * after the fixed columns (lengths, then the packed bytes), and a restore interns them into the
+ * fresh global dictionary before the GPU restore. Python mirror: flink_amd/two_phase.py
+ * (TwoPhaseSubtask), tested at world size 2.
  */
 package org.apache.flink.table.runtime.operators.window.gpu;
 
@@ -87,7 +96,9 @@ public final class GpuTwoPhaseWindowAggOperator extends TableStreamOperator<RowD
 
     private transient int maxP, parallelism, index;
     private transient long local, global;
-    private transient GpuKeyRows keys;
+    private transient GpuKeyRows keys;         // records -> ids of the local handle
+    private transient GpuKeyRows globalKeys;   // the global handle's dictionary (ids handed out by the edge)
+    private transient int keyHash;             // KEYHASH_BINARYROW_BIGINT, or KEYHASH_DICT_ID for dictionary keys
     private transient GpuAccRows accRows;
     private transient ByteBuffer keyCol, timeCol, valCol, nullCol;
     private transient int count;
@@ -108,9 +119,6 @@ public final class GpuTwoPhaseWindowAggOperator extends TableStreamOperator<RowD
     private transient byte[][] snapshotImage;   // chunks of the image taken at the last barrier
 
     public GpuTwoPhaseWindowAggOperator(GpuWindowAggSpec spec, RowDataKeySelector keySelector) {
-        if (!spec.bigintKey) {
-            throw new IllegalArgumentException("the RCCL edge moves BIGINT grouping keys only");
-        }
         this.spec = spec;
         this.keySelector = keySelector;
     }
@@ -158,8 +166,10 @@ public final class GpuTwoPhaseWindowAggOperator extends TableStreamOperator<RowD
                         spec.tzTransitionsMs,
                         spec.tzOffsetsMs);
         // the global's images leave the GPU ordered by key group: a restore reads only its own chunks
-        FlinkGpu.snapshotGrouping(global, FlinkGpu.KEYHASH_BINARYROW_BIGINT);
+        keyHash = spec.bigintKey ? FlinkGpu.KEYHASH_BINARYROW_BIGINT : FlinkGpu.KEYHASH_DICT_ID;
+        FlinkGpu.snapshotGrouping(global, keyHash);
         keys = new GpuKeyRows(spec, maxP);
+        globalKeys = new GpuKeyRows(spec, maxP, false);
         accRows = new GpuAccRows(spec.aggs, spec.valType);
         int b = spec.batchRecords;
         keyCol = GpuKeyRows.direct(8L * b);
@@ -212,6 +222,9 @@ public final class GpuTwoPhaseWindowAggOperator extends TableStreamOperator<RowD
     public void processElement(StreamRecord<RowData> element) throws Exception {
         RowData row = element.getValue();
         RowData key = keySelector.getKey(row);
+        if (!keys.fits(key)) {
+            flushBatch();
+        }
         keys.add(key, count, keyCol);
         timeCol.putLong(8 * count, row.getTimestamp(spec.rowtimeIndex, 3).getMillisecond());
         if (spec.valueIndex >= 0) {
@@ -237,6 +250,7 @@ public final class GpuTwoPhaseWindowAggOperator extends TableStreamOperator<RowD
         lock.lock();
         try {
             check();
+            keys.intern(count, keyCol);   // (under the lock: the edge's commRoundBegin reads this dictionary)
             FlinkGpu.addBatch(
                     local,
                     keyCol,
@@ -303,7 +317,7 @@ public final class GpuTwoPhaseWindowAggOperator extends TableStreamOperator<RowD
             }
         }
         int nAggs = spec.aggs.length;
-        RowData[] keyRows = keys.rows(cols[0], (int) n);
+        RowData[] keyRows = globalKeys.rows(cols[0], (int) n);   // (the global handle's keys: its dictionary)
         for (int i = 0; i < n; i++) {
             byte nullMask = cols[3 + nAggs].get(i);
             GenericRowData aggs = new GenericRowData(nAggs + 2);
@@ -408,6 +422,9 @@ public final class GpuTwoPhaseWindowAggOperator extends TableStreamOperator<RowD
         if (keys != null) {
             keys.close();
         }
+        if (globalKeys != null) {
+            globalKeys.close();
+        }
     }
 
     // ---- the edge thread ---------------------------------------------------------------------------
@@ -429,6 +446,14 @@ public final class GpuTwoPhaseWindowAggOperator extends TableStreamOperator<RowD
             ByteBuffer id = GpuKeyRows.direct(FlinkGpu.COMM_ID_BYTES);
             id.put(commId).flip();
             comm = FlinkGpu.commOpen(spec.device, parallelism, index, id);
+            if (!spec.bigintKey) {   // the keyed edge: every partial row ships its key row
+                lock.lock();
+                try {
+                    FlinkGpu.commSetKeyDicts(comm, keys.dict(), globalKeys.dict());
+                } finally {
+                    lock.unlock();
+                }
+            }
             while (true) {
                 int mode;
                 lock.lock();
@@ -450,7 +475,7 @@ public final class GpuTwoPhaseWindowAggOperator extends TableStreamOperator<RowD
                                 comm,
                                 mode == FlinkGpu.ROUND_IDLE ? 0 : local,
                                 mode,
-                                FlinkGpu.KEYHASH_BINARYROW_BIGINT,
+                                keyHash,
                                 maxP,
                                 wmLocal,
                                 epoch);
@@ -509,7 +534,9 @@ public final class GpuTwoPhaseWindowAggOperator extends TableStreamOperator<RowD
     /**
      * the global's image (snapshotStateAsync + Wait), grouped by key group on the GPU
      * (snapshotGrouping), as chunks cut along key-group boundaries: [rows, timer wm, kgLo, kgHi,
-     * rows x 7 longs] each. A chunk lies inside one slice and holds whole key groups kgLo .. kgHi
+     * rows x 7 longs] each, followed for dictionary keys by the rows' key rows (rows int32 lengths,
+     * then the packed bytes, each row padded to 8: the ids mean nothing to a restarted subtask's
+     * dictionary). A chunk lies inside one slice and holds whole key groups kgLo .. kgHi
      * of it (a key group larger than a chunk is split into chunks of that one key group), so a
      * restore decodes only the chunks whose key groups it owns.
      */
@@ -548,8 +575,14 @@ public final class GpuTwoPhaseWindowAggOperator extends TableStreamOperator<RowD
         return out.toArray(new byte[0][]);
     }
 
-    private static byte[] chunk(ByteBuffer[] cols, long lo, long hi, long wm, int kgLo, int kgHi) {
-        ByteBuffer b = ByteBuffer.allocate(32 + 56 * (int) (hi - lo)).order(ByteOrder.LITTLE_ENDIAN);
+    private byte[] chunk(ByteBuffer[] cols, long lo, long hi, long wm, int kgLo, int kgHi) {
+        byte[] keyRows = new byte[0];
+        if (!spec.bigintKey && hi > lo) {   // (dictRows of the chunk's ids, from the global dictionary)
+            ByteBuffer ids = cols[0].duplicate();
+            ids.position((int) (8 * lo)).limit((int) (8 * hi));
+            keyRows = globalKeys.packed(ids.slice().order(ByteOrder.nativeOrder()), (int) (hi - lo));
+        }
+        ByteBuffer b = ByteBuffer.allocate(32 + 56 * (int) (hi - lo) + keyRows.length).order(ByteOrder.LITTLE_ENDIAN);
         b.putLong(hi - lo).putLong(wm).putLong(kgLo).putLong(kgHi);
         for (long i = lo; i < hi; i++) {
             for (int c = 0; c < 7; c++) {
@@ -557,6 +590,7 @@ public final class GpuTwoPhaseWindowAggOperator extends TableStreamOperator<RowD
                 b.putLong(col.getLong((int) (8 * i)));
             }
         }
+        b.put(keyRows);
         return b.array();
     }
 
@@ -565,7 +599,9 @@ public final class GpuTwoPhaseWindowAggOperator extends TableStreamOperator<RowD
      * of them), and only the chunks whose key groups [kgLo, kgHi] intersect this subtask's range are
      * decoded into the seven direct column buffers. If every decoded chunk lies inside the range,
      * they are the subtask's state as they are (fg_restore); else the global handle, opened with the
-     * range, drops the foreign rows of the boundary chunks on the GPU (fg_restore_range).
+     * range, drops the foreign rows of the boundary chunks on the GPU (fg_restore_range). For
+     * dictionary keys the chunks' key rows are interned into the fresh global dictionary first
+     * (internPacked) and the ids it hands out replace the key column.
      */
     private void restoreGlobal(KeyGroupRange range) {
         if (restoredImage == null || restoredImage.isEmpty()) {
@@ -595,10 +631,23 @@ public final class GpuTwoPhaseWindowAggOperator extends TableStreamOperator<RowD
         int at = 0;
         for (ByteBuffer b : mine) {
             long rows = b.getLong(0);
+            int first = at;
             for (long i = 0; i < rows; i++, at++) {
                 for (int j = 0; j < 7; j++) {
                     c[j].putLong(8 * at, b.getLong());
                 }
+            }
+            if (!spec.bigintKey) {   // [lengths int32 x rows][packed key rows]: ids of the fresh dictionary
+                ByteBuffer len = GpuKeyRows.direct(4L * rows);
+                for (long i = 0; i < rows; i++) {
+                    len.putInt((int) (4 * i), b.getInt());
+                }
+                int nbytes = b.remaining();
+                ByteBuffer packed = GpuKeyRows.direct(nbytes);
+                packed.put(b).position(0);
+                ByteBuffer ids = c[0].duplicate();
+                ids.position(8 * first).limit(8 * at);
+                globalKeys.internPacked(packed, nbytes, len, (int) rows, ids.slice().order(ByteOrder.nativeOrder()));
             }
         }
         boolean mv = accRows.multiValue();
@@ -607,7 +656,7 @@ public final class GpuTwoPhaseWindowAggOperator extends TableStreamOperator<RowD
             FlinkGpu.restore(global, n, c[0], c[1], c[2], c[3], c[4], min, max, timerWm);
         } else {
             FlinkGpu.restoreRange(
-                    global, n, c[0], c[1], c[2], c[3], c[4], min, max, FlinkGpu.KEYHASH_BINARYROW_BIGINT, timerWm);
+                    global, n, c[0], c[1], c[2], c[3], c[4], min, max, keyHash, timerWm);
         }
         restoredImage = null;
     }

@@ -660,6 +660,14 @@ JNIEXPORT void JNICALL FN(commRoundEnd)(JNIEnv* env, jclass cls, jlong cp, jlong
     (void)ccheck(env, c, fg_comm_round_end(c, (fg_handle*)(intptr_t)gp));
 }
 
+/* void commSetKeyDicts(long comm, long localDict, long globalDict): fg_comm_set_key_dicts -- rounds
+ * with KEYHASH_DICT_ID ship each row's key row from now on (0, 0 detaches) */
+JNIEXPORT void JNICALL FN(commSetKeyDicts)(JNIEnv* env, jclass cls, jlong cp, jlong ldp, jlong gdp) {
+    (void)cls;
+    fg_comm* c = (fg_comm*)(intptr_t)cp;
+    (void)ccheck(env, c, fg_comm_set_key_dicts(c, (fg_key_dict*)(intptr_t)ldp, (fg_key_dict*)(intptr_t)gdp));
+}
+
 /* long commBytesSent(long comm) */
 JNIEXPORT jlong JNICALL FN(commBytesSent)(JNIEnv* env, jclass cls, jlong cp) {
     (void)env;
