@@ -248,6 +248,32 @@ struct PendingBatch {
     int slot = -1;
 };
 
+// The slices of a snapshot plan or image (fg_image_slices): ends, row ranges, changed flags
+struct SliceList {
+    std::vector<int64_t> se, first, rows;
+    std::vector<uint8_t> changed;
+    size_t size() const { return se.size(); }
+    void clear() {
+        se.clear();
+        first.clear();
+        rows.clear();
+        changed.clear();
+    }
+    void add(int64_t slice_end, int64_t first_row, int64_t n, uint8_t ch) {
+        se.push_back(slice_end);
+        first.push_back(first_row);
+        rows.push_back(n);
+        changed.push_back(ch);
+    }
+    void point(fg_image_slices* out) const {
+        out->n = (int64_t)se.size();
+        out->slice_end = se.data();
+        out->first_row = first.data();
+        out->rows = rows.data();
+        out->changed = changed.data();
+    }
+};
+
 struct fg_handle {
     int32_t kvt = 0;   // kernel value op (val_type | op << 2); multi-value: the value type
     // several value accumulators (SUM family + MIN + MAX): value slots 0 SUM, 1 MIN, 2 MAX
@@ -307,32 +333,32 @@ struct fg_handle {
     // stream after the export kernels (event ev_snap), collected by fg_snapshot_state_wait
     hipStream_t snap_stream = nullptr;
     hipEvent_t ev_snap = nullptr;
-    bool snap_pending = false;
-    bool snap_cv_alias = false;   // the pending image's cnt_val column is its cnt_star column
-    int64_t snap_total = 0, snap_wm = 0;
-    // the slices of the last image (fg_snapshot_slices): ends, row ranges, changed since the image
-    // before (SliceTable.changed, cleared at each snapshot)
-    std::vector<int64_t> img_se, img_first, img_rows;
-    std::vector<uint8_t> img_changed;
-    bool img_ready = false;   // an image was returned since the last snapshot call
-    // key-grouped images (fg_set_snapshot_grouping): the key hash (< 0: off), the second column set
-    // the export's rows are scattered into (the D2H source), the (slice, key group) counters and
-    // offsets, and the last image's index (fg_snapshot_key_groups)
-    int32_t snap_group = -1;
-    bool snap_grouped = false;   // the pending / last image is grouped
-    int64_t snap_bins = 0;       // its slices x max_parallelism
+    // snapshot state (fg_snapshot_*): the image on its way to the host, the last image's slices and
+    // key-group index, the last plan
+    struct Snapshot {
+        bool pending = false;    // an image is queued and not collected (fg_snapshot_state_wait)
+        bool cv_alias = false;   // the pending image's cnt_val column is its cnt_star column
+        int64_t total = 0, wm = 0;
+        // the slices of the last image (fg_snapshot_slices): changed since the image before
+        // (SliceTable.changed, cleared at each snapshot)
+        SliceList img;
+        bool img_ready = false;   // an image was returned since the last snapshot call
+        // key-grouped images (fg_set_snapshot_grouping): the key hash (< 0: off) and the last image's
+        // index (fg_snapshot_key_groups)
+        int32_t group = -1;
+        bool grouped = false;   // the pending / last image is grouped
+        int64_t bins = 0;       // its slices x max_parallelism
+        std::vector<int64_t> img_kg_first;
+        // the resident slices as the last fg_snapshot_plan listed them (its region counts stay in
+        // hs_counts) -- valid until a call that may change the state, consumed by an export
+        bool plan_valid = false;
+        int64_t plan_wm = 0;
+        SliceList plan;
+    } snap;
+    // key-grouped images: the second column set the export's rows are scattered into (the D2H
+    // source), the (slice, key group) counters and offsets
     DevBuf g_key, g_cs, g_cv, g_sum, g_v1, g_v2, kg_first, kg_cnt, kg_off, kg_tmp;
     HostBuf hs_kg_first, hs_kg_off;
-    std::vector<int64_t> img_kg_first;
-    // selective images (fg_snapshot_plan / fg_snapshot_state_select_async): the resident slices as
-    // the last plan listed them (its region counts stay in hs_counts) -- valid until a call that
-    // may change the state, consumed by a select; the select's table descriptors
-    bool plan_valid = false;
-    int64_t plan_wm = 0;
-    std::vector<int64_t> plan_se, plan_first, plan_rows;
-    std::vector<uint8_t> plan_changed;
-    DevBuf sel_tab;
-    HostBuf hs_sel_tab;
     DevBuf hb_key[2], hb_ts[2], hb_val[2], hb_null[2];
     DevBuf hb_narrow[2];   // FG_HOST narrow columns (fg_batch.format) before widening
     hipEvent_t ev_copied[2] = {nullptr, nullptr}, ev_free[2] = {nullptr, nullptr};
@@ -3647,7 +3673,7 @@ int fg_open(const fg_config* cfg, fg_handle** out) {
 
 int fg_add_batch(fg_handle* h, const fg_batch* b) {
     if (!h || !b) return FG_EINVAL;
-    h->plan_valid = false;
+    h->snap.plan_valid = false;
     if (b->n <= 0) return FG_OK;
     if (b->n > (int64_t)0x7fffffff) return h->fail(FG_EINVAL, "batch larger than 2^31-1 records");
     if (!b->key || !b->rowtime) return h->fail(FG_EINVAL, "batch key/rowtime columns are required");
@@ -3816,7 +3842,7 @@ int fg_add_batch(fg_handle* h, const fg_batch* b) {
 
 int fg_add_rows(fg_handle* h, const fg_row_batch* b) {
     if (!h || !b) return FG_EINVAL;
-    h->plan_valid = false;
+    h->snap.plan_valid = false;
     if (b->n <= 0) return FG_OK;
     if (b->n > (int64_t)0x7fffffff) return h->fail(FG_EINVAL, "batch larger than 2^31-1 rows");
     if (!b->rows) return h->fail(FG_EINVAL, "rows pointer is required");
@@ -3891,7 +3917,7 @@ static int add_partials(fg_handle* h, const fg_partials* b) {
     if (h) {
         h->cnt_bound = JMAX;
         h->keys32 = false;
-        h->plan_valid = false;
+        h->snap.plan_valid = false;
     }
     if (!h || !b) return FG_EINVAL;
     if (b->n <= 0) return FG_OK;
@@ -3958,7 +3984,7 @@ static int add_partials(fg_handle* h, const fg_partials* b) {
 
 int fg_flush(fg_handle* h) {
     if (!h) return FG_EINVAL;
-    h->plan_valid = false;
+    h->snap.plan_valid = false;
     HIPCHK(h, hipSetDevice(h->device));
     if (int rc0 = settle_pending(h)) return rc0;
     return flush(h);
@@ -4100,7 +4126,7 @@ static void quiet_progress(fg_handle* h, int64_t wm) {   // advance()'s bookkeep
 
 int fg_advance_progress_async(fg_handle* h, int64_t wm) {
     if (!h) return FG_EINVAL;
-    h->plan_valid = false;
+    h->snap.plan_valid = false;
     HIPCHK(h, hipSetDevice(h->device));
     if (quiet_advance(h, wm)) {
         quiet_progress(h, wm);
@@ -4124,7 +4150,7 @@ int fg_advance_progress_async(fg_handle* h, int64_t wm) {
 
 int fg_advance_progress_async_n(fg_handle* h, const int64_t* wms, int64_t n) {
     if (!h || n < 0 || (n > 0 && !wms)) return FG_EINVAL;
-    h->plan_valid = false;
+    h->snap.plan_valid = false;
     for (int64_t i = 0; i < n; i++)
         if (int rc = fg_advance_progress_async(h, wms[i])) return rc;
     return FG_OK;
@@ -4145,7 +4171,7 @@ static void device_rows(fg_handle* h, int32_t out_location, fg_rows* fired) {
 
 int fg_collect_fired_to(fg_handle* h, int32_t out_location, fg_rows* fired) {
     if (!h || !fired || (out_location != FG_HOST && out_location != FG_DEVICE)) return FG_EINVAL;
-    h->plan_valid = false;
+    h->snap.plan_valid = false;
     HIPCHK(h, hipSetDevice(h->device));
     if (int rc = complete_fire(h)) return rc;
     if (!h->async_open) h->out_n = 0;   // (every async advance since the last collect fired nothing)
@@ -4165,7 +4191,7 @@ int fg_collect_fired(fg_handle* h, fg_rows* fired) { return fg_collect_fired_to(
 
 int fg_flush_partials(fg_handle* h, int32_t out_location, fg_rows* fired) {
     if (!h || !fired || (out_location != FG_HOST && out_location != FG_DEVICE)) return FG_EINVAL;
-    h->plan_valid = false;
+    h->snap.plan_valid = false;
     if (!h->local) return h->fail(FG_ESTATE, "fg_flush_partials on an operator without FG_FLAG_LOCAL_PARTIALS");
     HIPCHK(h, hipSetDevice(h->device));
     h->local_emit_all = true;
@@ -4185,7 +4211,7 @@ int fg_flush_partials(fg_handle* h, int32_t out_location, fg_rows* fired) {
 
 int fg_advance_progress(fg_handle* h, int64_t wm, int32_t out_location, fg_rows* fired) {
     if (!h) return FG_EINVAL;
-    h->plan_valid = false;
+    h->snap.plan_valid = false;
     HIPCHK(h, hipSetDevice(h->device));
     int rc = advance_progress(h, wm);   // (uncollected async rows lead its rows: adv_base)
     if (rc) return rc;
@@ -4206,19 +4232,19 @@ int fg_advance_progress(fg_handle* h, int64_t wm, int32_t out_location, fg_rows*
     return FG_OK;
 }
 
-// fg_set_snapshot_grouping: the exported image (s_*, `total` rows in the slices of img_first)
+// fg_set_snapshot_grouping: the exported image (s_*, `total` rows in the slices of snap.img)
 // reordered by key group inside every slice into the second column set (g_*) on the handle's
 // stream; kg_off: the row offset of every (slice, key group). The slice_end column keeps its
 // place (a row stays in its slice), and an aliased cnt_val column is not moved.
 static int snapshot_group(fg_handle* h, int64_t total, bool any_null) {
-    const int64_t S = (int64_t)h->img_se.size(), maxp = h->cfg.max_parallelism;
+    const int64_t S = (int64_t)h->snap.img.size(), maxp = h->cfg.max_parallelism;
     if (S * maxp > kKgMaxBins || total >= ((int64_t)1 << 32))
         return h->fail(FG_EINVAL, "grouped snapshot: more than 2^30 (slice, key group) pairs or 2^32 rows");
-    h->snap_bins = S * maxp;
+    h->snap.bins = S * maxp;
     if (total == 0) return FG_OK;
-    const int64_t bins = h->snap_bins;
+    const int64_t bins = h->snap.bins;
     HIPCHK(h, h->hs_kg_first.ensure(8 * (size_t)(S + 1)));
-    for (int64_t s = 0; s < S; s++) h->hs_kg_first.as<int64_t>()[s] = h->img_first[(size_t)s];
+    for (int64_t s = 0; s < S; s++) h->hs_kg_first.as<int64_t>()[s] = h->snap.img.first[(size_t)s];
     h->hs_kg_first.as<int64_t>()[S] = total;
     HIPCHK(h, h->kg_first.ensure(8 * (size_t)(S + 1)));
     HIPCHK(h, h->kg_cnt.ensure(4 * (size_t)bins));
@@ -4232,7 +4258,7 @@ static int snapshot_group(fg_handle* h, int64_t total, bool any_null) {
     p.slice_first = h->kg_first.as<int64_t>();
     p.n_slices = (int32_t)S;
     p.grid = rr_grid(total);
-    p.key_hash = h->snap_group;
+    p.key_hash = h->snap.group;
     p.max_p = (int32_t)maxp;
     p.cnt = h->kg_cnt.as<uint32_t>();
     p.off = h->kg_off.as<uint32_t>();
@@ -4313,17 +4339,17 @@ static int snapshot_columns(fg_handle* h, int64_t total) {
     return FG_OK;
 }
 
-// The back half of a snapshot: the exported image (s_*, `total` rows in the slices of img_se /
-// img_first) grouped by key group if the grouping is on, and its copy into the pinned host image
+// The back half of a snapshot: the exported image (s_*, `total` rows in the slices of
+// snap.img) grouped by key group if the grouping is on, and its copy into the pinned host image
 // (hs_*) queued on the snapshot stream. any_null: some exported table counts NULL values (else
 // the cnt_val column was not needed and is neither moved nor copied).
 static int snapshot_queue(fg_handle* h, int64_t total, bool any_null) {
-    h->snap_grouped = h->snap_group >= 0;
+    h->snap.grouped = h->snap.group >= 0;
     const int64_t *d_key = h->s_key.as<int64_t>(), *d_cs = h->s_cs.as<int64_t>(), *d_cv = h->s_cv.as<int64_t>(),
                   *d_sum = h->s_sum.as<int64_t>(), *d_v1 = h->s_v1.as<int64_t>(), *d_v2 = h->s_v2.as<int64_t>();
-    if (h->snap_grouped) {
+    if (h->snap.grouped) {
         if (int rcg = snapshot_group(h, total, any_null)) {
-            h->snap_grouped = false;
+            h->snap.grouped = false;
             return rcg;
         }
         if (total > 0) {
@@ -4352,135 +4378,71 @@ static int snapshot_queue(fg_handle* h, int64_t total, bool any_null) {
         HIPCHK(h, hipMemcpyAsync(h->hs_cs.p, d_cs, 8 * total, kd, cs));
         // no table counts NULL values: COUNT(v) = COUNT(*) for every entry, and the image's
         // cnt_val column is its cnt_star column (a fifth less to copy while the job runs on)
-        h->snap_cv_alias = !any_null;
+        h->snap.cv_alias = !any_null;
         if (any_null) HIPCHK(h, hipMemcpyAsync(h->hs_cv.p, d_cv, 8 * total, kd, cs));
         HIPCHK(h, hipMemcpyAsync(h->hs_sum.p, d_sum, 8 * total, kd, cs));
-        if (h->snap_grouped)   // the index travels with the image
-            HIPCHK(h, hipMemcpyAsync(h->hs_kg_off.p, h->kg_off.p, 4 * (size_t)(h->snap_bins + 1), kd, cs));
+        if (h->snap.grouped)   // the index travels with the image
+            HIPCHK(h, hipMemcpyAsync(h->hs_kg_off.p, h->kg_off.p, 4 * (size_t)(h->snap.bins + 1), kd, cs));
     }
-    h->snap_pending = true;
-    h->snap_total = total;
-    h->snap_wm = h->timer_wm;
+    h->snap.pending = true;
+    h->snap.total = total;
+    h->snap.wm = h->timer_wm;
     return FG_OK;
-}
-
-// snapshotState's synchronous part: the staged records flushed, every resident slice exported
-// into the device image columns (s_*, in stream order: the image is the state as of this call)
-// and their copy into the pinned host image (hs_*) queued on the snapshot stream
-static int snapshot_begin(fg_handle* h) {
-    std::vector<int64_t> rows;
-    int rc = snapshot_counts(h, rows);
-    if (rc) return rc;
-    const size_t nt = h->tables.size();
-    int64_t total = 0;
-    HIPCHK(h, h->hs_off.ensure(sizeof(uint64_t) * h->P * std::max<size_t>(nt, 1)));
-    for (size_t t = 0; t < nt; t++) {
-        for (int r = 0; r < h->P; r++) {
-            h->hs_off.as<uint64_t>()[t * h->P + r] = (uint64_t)total;
-            total += h->hs_counts.as<uint32_t>()[t * h->P + r];
-        }
-    }
-    // the image's slices: its rows are grouped by slice, in the tables' (ascending) order
-    h->img_ready = false;
-    h->img_se.clear();
-    h->img_first.clear();
-    h->img_rows.clear();
-    h->img_changed.clear();
-    bool any_null = false;
-    {
-        size_t t = 0;
-        for (auto& kv : h->tables) {
-            h->img_se.push_back(kv.first);
-            h->img_first.push_back((int64_t)h->hs_off.as<uint64_t>()[t * h->P]);
-            h->img_rows.push_back(rows[t]);
-            h->img_changed.push_back(kv.second->changed ? 1 : 0);
-            kv.second->changed = false;
-            any_null = any_null || kv.second->has_null;
-            t++;
-        }
-    }
-    if (int rcc = snapshot_columns(h, total)) return rcc;
-    HIPCHK(h, h->s_off.ensure(sizeof(uint64_t) * h->P * std::max<size_t>(nt, 1)));
-    HIPCHK(h, hipMemcpyAsync(h->s_off.p, h->hs_off.p, sizeof(uint64_t) * h->P * nt, hipMemcpyHostToDevice, h->stream));
-    size_t ti = 0;
-    for (auto& kv : h->tables) {
-        ExportParams p{};
-        p.t = ref_of(kv.second.get());
-        p.region_off = h->s_off.as<uint64_t>() + ti * h->P;
-        p.slice_end = kv.first;
-        p.out_key = h->s_key.as<int64_t>();
-        p.out_slice = h->s_slice.as<int64_t>();
-        p.out_cnt_star = h->s_cs.as<int64_t>();
-        p.out_cnt_val = h->s_cv.as<int64_t>();
-        p.out_sum = h->s_sum.as<int64_t>();
-        p.mv = h->mv;
-        p.out_v1 = h->s_v1.as<int64_t>();
-        p.out_v2 = h->s_v2.as<int64_t>();
-        {
-            KTimer kt(h, K_EXPORT, 0);
-            HIPCHK(h, launch_export(p, h->P, h->stream));
-        }
-        ti++;
-    }
-    return snapshot_queue(h, total, any_null);
 }
 
 // fg_snapshot_plan: the resident slices and what a full image taken now would hold of them
 static int snapshot_plan(fg_handle* h) {
-    h->plan_valid = false;
+    fg_handle::Snapshot& s = h->snap;
+    s.plan_valid = false;
     std::vector<int64_t> rows;
     if (int rc = snapshot_counts(h, rows)) return rc;
-    h->plan_se.clear();
-    h->plan_first.clear();
-    h->plan_changed.clear();
+    s.plan.clear();
     int64_t total = 0;
     size_t t = 0;
     for (auto& kv : h->tables) {
-        h->plan_se.push_back(kv.first);
-        h->plan_first.push_back(total);
-        h->plan_changed.push_back(kv.second->changed ? 1 : 0);
+        s.plan.add(kv.first, total, rows[t], kv.second->changed ? 1 : 0);
         total += rows[t++];
     }
-    h->plan_rows = std::move(rows);
-    h->plan_wm = h->timer_wm;
-    h->plan_valid = true;
+    s.plan_wm = h->timer_wm;
+    s.plan_valid = true;
     return FG_OK;
 }
 
-// fg_snapshot_state_select_async: the planned slices with want[i] != 0 exported by one k_export_sel
-// launch into a compact image. The descriptors and the 64-bit region offsets come from the counts
-// the plan read (hs_counts): nothing is read back between this call and the launch.
-static int snapshot_select(fg_handle* h, const uint8_t* want, int64_t n) {
-    if (!h->plan_valid) return h->fail(FG_ESTATE, "fg_snapshot_state_select: no valid fg_snapshot_plan (a call since the plan may have changed the state)");
-    const size_t nt = h->plan_se.size();
-    if (n != (int64_t)nt)
-        return h->fail(FG_EINVAL, "fg_snapshot_state_select: n = %lld, the plan lists %lld slices", (long long)n, (long long)nt);
-    if (n > 0 && !want) return h->fail(FG_EINVAL, "fg_snapshot_state_select: want is NULL");
+// snapshotState's synchronous part after the (valid) plan: the planned slices with want[i] != 0 (want ==
+// nullptr: every one, the full image) exported by one k_export_sel launch into the compact device
+// image (s_*, in stream order: the image is the state as of the plan), and its copy into the pinned
+// host image (hs_*) queued on the snapshot stream. The descriptors and the 64-bit region offsets
+// come from the counts the plan read (hs_counts): nothing is read back between the plan and the
+// launch. `fn`: the entry point, for messages.
+static int snapshot_export(fg_handle* h, const char* fn, const uint8_t* want) {
+    fg_handle::Snapshot& s = h->snap;
+    const size_t nt = s.plan.size();
     int64_t total = 0;
     size_t nsel = 0;
     for (size_t t = 0; t < nt; t++) {
-        if (!want[t]) continue;
+        if (want && !want[t]) continue;
         nsel++;
-        total += h->plan_rows[t];
-        if (total >= ((int64_t)1 << 32)) return h->fail(FG_EINVAL, "fg_snapshot_state_select: 2^32 or more selected rows");
+        total += s.plan.rows[t];
     }
-    if (nsel > 65535) return h->fail(FG_EINVAL, "fg_snapshot_state_select: more than 65535 selected slices");
-    h->plan_valid = false;   // consumed
+    if (total >= ((int64_t)1 << 32)) return h->fail(FG_EINVAL, "%s: 2^32 or more rows in one image", fn);
+    if (nsel > 65535) return h->fail(FG_EINVAL, "%s: more than 65535 slices in one image", fn);
+    s.plan_valid = false;   // consumed
     const size_t P = (size_t)h->P;
-    HIPCHK(h, h->hs_sel_tab.ensure(sizeof(ExportSelTable) * std::max<size_t>(nsel, 1)));
-    HIPCHK(h, h->hs_off.ensure(sizeof(uint64_t) * (P + 1) * std::max<size_t>(nsel, 1)));
-    h->img_ready = false;
-    h->img_se.clear();
-    h->img_first.clear();
-    h->img_rows.clear();
-    h->img_changed.clear();
+    // the tables' region offsets, then their descriptors, in one buffer and one host-to-device copy
+    // (with a second small copy the barrier was measured slower: DESIGN.md 7d, "One export path")
+    const size_t off_bytes = sizeof(uint64_t) * (P + 1) * nsel, up_bytes = off_bytes + sizeof(ExportSelTable) * nsel;
+    HIPCHK(h, h->hs_off.ensure(std::max<size_t>(up_bytes, 8)));
+    ExportSelTable* const desc = reinterpret_cast<ExportSelTable*>(h->hs_off.as<char>() + off_bytes);
+    // the image's slices: its rows are grouped by slice, in the tables' (ascending) order
+    s.img_ready = false;
+    s.img.clear();
     bool any_null = false;
     {
         size_t t = 0, j = 0;
         int64_t base = 0;
         for (auto& kv : h->tables) {
-            if (want[t]) {
-                ExportSelTable& d = h->hs_sel_tab.as<ExportSelTable>()[j];
+            if (!want || want[t]) {
+                ExportSelTable& d = desc[j];
                 d.t = ref_of(kv.second.get());
                 d.slice_end = kv.first;
                 d.row_base = base;
@@ -4491,13 +4453,10 @@ static int snapshot_select(fg_handle* h, const uint8_t* want, int64_t n) {
                     o += h->hs_counts.as<uint32_t>()[t * P + r];
                 }
                 off[P] = o;
-                h->img_se.push_back(kv.first);
-                h->img_first.push_back(base);
-                h->img_rows.push_back(h->plan_rows[t]);
-                h->img_changed.push_back(h->plan_changed[t]);
+                s.img.add(kv.first, base, s.plan.rows[t], s.plan.changed[t]);
                 kv.second->changed = false;
                 any_null = any_null || kv.second->has_null;
-                base += h->plan_rows[t];
+                base += s.plan.rows[t];
                 j++;
             }
             t++;
@@ -4505,12 +4464,10 @@ static int snapshot_select(fg_handle* h, const uint8_t* want, int64_t n) {
     }
     if (int rcc = snapshot_columns(h, total)) return rcc;
     if (nsel > 0) {
-        HIPCHK(h, h->sel_tab.ensure(sizeof(ExportSelTable) * nsel));
-        HIPCHK(h, h->s_off.ensure(sizeof(uint64_t) * (P + 1) * nsel));
-        HIPCHK(h, hipMemcpyAsync(h->sel_tab.p, h->hs_sel_tab.p, sizeof(ExportSelTable) * nsel, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->s_off.p, h->hs_off.p, sizeof(uint64_t) * (P + 1) * nsel, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, h->s_off.ensure(up_bytes));
+        HIPCHK(h, hipMemcpyAsync(h->s_off.p, h->hs_off.p, up_bytes, hipMemcpyHostToDevice, h->stream));
         ExportSelParams p{};
-        p.tables = h->sel_tab.as<ExportSelTable>();
+        p.tables = reinterpret_cast<const ExportSelTable*>(h->s_off.as<char>() + off_bytes);
         p.region_off = h->s_off.as<uint64_t>();
         p.regions = h->P;
         p.n_tables = (int32_t)nsel;
@@ -4523,7 +4480,7 @@ static int snapshot_select(fg_handle* h, const uint8_t* want, int64_t n) {
         p.out_v2 = h->s_v2.as<int64_t>();
         p.mv = h->mv;
         p.with_cv = any_null ? 1 : 0;
-        KTimer kt(h, K_EXPORT_SELECT, total);
+        KTimer kt(h, want ? K_EXPORT_SELECT : K_EXPORT, total);
         HIPCHK(h, launch_export_sel(p, h->stream));
     }
     return snapshot_queue(h, total, any_null);
@@ -4531,113 +4488,126 @@ static int snapshot_select(fg_handle* h, const uint8_t* want, int64_t n) {
 
 // snapshotState's asynchronous part: the host image once its copy has completed
 static int snapshot_end(fg_handle* h, fg_state_rows* out, int64_t* timer_watermark) {
-    if (!h->snap_pending) return h->fail(FG_ESTATE, "fg_snapshot_state_wait without fg_snapshot_state_async");
+    if (!h->snap.pending) return h->fail(FG_ESTATE, "fg_snapshot_state_wait without fg_snapshot_state_async");
     if (h->snap_stream) HIPCHK(h, hipStreamSynchronize(h->snap_stream));
-    h->snap_pending = false;
-    const int64_t total = h->snap_total;
+    h->snap.pending = false;
+    const int64_t total = h->snap.total;
     out->n = total;
     out->key = h->hs_key.as<int64_t>();
     out->slice_end = h->hs_slice.as<int64_t>();
     out->cnt_star = h->hs_cs.as<int64_t>();
-    out->cnt_val = h->snap_cv_alias ? h->hs_cs.as<int64_t>() : h->hs_cv.as<int64_t>();
+    out->cnt_val = h->snap.cv_alias ? h->hs_cs.as<int64_t>() : h->hs_cv.as<int64_t>();
     out->sum = h->hs_sum.as<int64_t>();
     out->min = h->mv ? h->hs_v1.as<int64_t>() : nullptr;   // multi-value operators: the MIN / MAX slots
     out->max = h->mv ? h->hs_v2.as<int64_t>() : nullptr;
-    if (timer_watermark) *timer_watermark = h->snap_wm;
-    if (h->snap_grouped) {   // the index: the scanned counters, widened (an image without rows: all 0)
-        h->img_kg_first.assign((size_t)h->snap_bins + 1, 0);
+    if (timer_watermark) *timer_watermark = h->snap.wm;
+    if (h->snap.grouped) {   // the index: the scanned counters, widened (an image without rows: all 0)
+        h->snap.img_kg_first.assign((size_t)h->snap.bins + 1, 0);
         if (total > 0)
-            for (int64_t i = 0; i <= h->snap_bins; i++) h->img_kg_first[(size_t)i] = h->hs_kg_off.as<uint32_t>()[i];
+            for (int64_t i = 0; i <= h->snap.bins; i++) h->snap.img_kg_first[(size_t)i] = h->hs_kg_off.as<uint32_t>()[i];
     }
-    h->img_ready = true;
+    h->snap.img_ready = true;
     return FG_OK;
 }
 
 int fg_set_snapshot_grouping(fg_handle* h, int32_t key_hash) {
     if (!h) return FG_EINVAL;
-    h->plan_valid = false;
+    h->snap.plan_valid = false;
     if (key_hash >= 0 && key_hash != FG_KEYHASH_BINARYROW_BIGINT && key_hash != FG_KEYHASH_JAVA_LONG &&
         key_hash != FG_KEYHASH_DICT_ID)
         return h->fail(FG_EINVAL, "fg_set_snapshot_grouping: unknown key_hash %d", key_hash);
     if (key_hash >= 0 && (h->cfg.max_parallelism < 1 || h->cfg.max_parallelism > 32768))
         return h->fail(FG_EINVAL, "fg_set_snapshot_grouping: max_parallelism %d is not in 1 .. 32768", h->cfg.max_parallelism);
-    if (h->snap_pending)
+    if (h->snap.pending)
         return h->fail(FG_EINVAL, "fg_set_snapshot_grouping: an asynchronous snapshot is not collected yet");
-    h->snap_group = key_hash < 0 ? -1 : key_hash;
+    h->snap.group = key_hash < 0 ? -1 : key_hash;
     return FG_OK;
 }
 
 int fg_snapshot_key_groups(fg_handle* h, fg_image_key_groups* out) {
     if (!h || !out) return FG_EINVAL;
-    h->plan_valid = false;
-    if (!h->img_ready) return h->fail(FG_ESTATE, "fg_snapshot_key_groups: no image returned since the last snapshot call");
-    if (!h->snap_grouped) return h->fail(FG_ESTATE, "fg_snapshot_key_groups: the image was taken with grouping off");
-    out->n_slices = (int64_t)h->img_se.size();
+    h->snap.plan_valid = false;
+    if (!h->snap.img_ready) return h->fail(FG_ESTATE, "fg_snapshot_key_groups: no image returned since the last snapshot call");
+    if (!h->snap.grouped) return h->fail(FG_ESTATE, "fg_snapshot_key_groups: the image was taken with grouping off");
+    out->n_slices = (int64_t)h->snap.img.size();
     out->max_parallelism = h->cfg.max_parallelism;
-    out->first_row = h->img_kg_first.data();
+    out->first_row = h->snap.img_kg_first.data();
     return FG_OK;
 }
 
 int fg_snapshot_slices(fg_handle* h, fg_image_slices* out) {
     if (!h || !out) return FG_EINVAL;
-    h->plan_valid = false;
-    if (!h->img_ready) return h->fail(FG_ESTATE, "fg_snapshot_slices: no image returned since the last snapshot call");
-    out->n = (int64_t)h->img_se.size();
-    out->slice_end = h->img_se.data();
-    out->first_row = h->img_first.data();
-    out->rows = h->img_rows.data();
-    out->changed = h->img_changed.data();
+    h->snap.plan_valid = false;
+    if (!h->snap.img_ready) return h->fail(FG_ESTATE, "fg_snapshot_slices: no image returned since the last snapshot call");
+    h->snap.img.point(out);
     return FG_OK;
 }
 
-int fg_snapshot_state_async(fg_handle* h) {
+// What the calls that start a snapshot or a plan check first: a handle, its device, no image on its
+// way to the host. `fn`: the entry point, for the message.
+static int snapshot_enter(fg_handle* h, const char* fn) {
     if (!h) return FG_EINVAL;
-    h->plan_valid = false;
     HIPCHK(h, hipSetDevice(h->device));
-    if (h->snap_pending) return h->fail(FG_ESTATE, "an asynchronous snapshot is not collected yet (fg_snapshot_state_wait)");
-    return snapshot_begin(h);
+    if (h->snap.pending)
+        return h->fail(FG_ESTATE, "%s: an asynchronous snapshot is not collected yet (fg_snapshot_state_wait)", fn);
+    return FG_OK;
+}
+
+// fg_snapshot_state[_async]: a plan of its own and every slice of it exported. No plan is valid after it.
+static int snapshot_full(fg_handle* h, const char* fn) {
+    if (int rc = snapshot_enter(h, fn)) return rc;
+    if (int rc = snapshot_plan(h)) return rc;
+    const int rc = snapshot_export(h, fn, nullptr);
+    h->snap.plan_valid = false;   // (an export that failed its limits leaves its plan)
+    return rc;
+}
+
+// fg_snapshot_state_select[_async]: the caller's mask checked against the caller's plan, and exported
+static int snapshot_select(fg_handle* h, const char* fn, const uint8_t* want, int64_t n) {
+    if (int rc = snapshot_enter(h, fn)) return rc;
+    if (!h->snap.plan_valid)
+        return h->fail(FG_ESTATE, "%s: no valid fg_snapshot_plan (a call since the plan may have changed the state)", fn);
+    const int64_t nt = (int64_t)h->snap.plan.size();
+    if (n != nt) return h->fail(FG_EINVAL, "%s: n = %lld, the plan lists %lld slices", fn, (long long)n, (long long)nt);
+    if (n > 0 && !want) return h->fail(FG_EINVAL, "%s: want is NULL", fn);
+    return snapshot_export(h, fn, want);
+}
+
+int fg_snapshot_state_async(fg_handle* h) {
+    if (h) h->snap.plan_valid = false;
+    return snapshot_full(h, "fg_snapshot_state_async");
 }
 
 int fg_snapshot_state_wait(fg_handle* h, fg_state_rows* out, int64_t* timer_watermark) {
     if (!h || !out) return FG_EINVAL;
-    h->plan_valid = false;
+    h->snap.plan_valid = false;
     HIPCHK(h, hipSetDevice(h->device));
     return snapshot_end(h, out, timer_watermark);
 }
 
 int fg_snapshot_state(fg_handle* h, fg_state_rows* out, int64_t* timer_watermark) {
     if (!h || !out) return FG_EINVAL;
-    h->plan_valid = false;
-    HIPCHK(h, hipSetDevice(h->device));
-    if (h->snap_pending) return h->fail(FG_ESTATE, "an asynchronous snapshot is not collected yet (fg_snapshot_state_wait)");
-    if (int rc = snapshot_begin(h)) return rc;
+    h->snap.plan_valid = false;
+    if (int rc = snapshot_full(h, "fg_snapshot_state")) return rc;
     return snapshot_end(h, out, timer_watermark);
 }
 
 int fg_snapshot_plan(fg_handle* h, fg_image_slices* out, int64_t* timer_watermark) {
-    if (!h || !out) return FG_EINVAL;
-    HIPCHK(h, hipSetDevice(h->device));
-    if (h->snap_pending) return h->fail(FG_ESTATE, "an asynchronous snapshot is not collected yet (fg_snapshot_state_wait)");
+    if (!out) return FG_EINVAL;
+    if (int rc = snapshot_enter(h, "fg_snapshot_plan")) return rc;
     if (int rc = snapshot_plan(h)) return rc;
-    out->n = (int64_t)h->plan_se.size();
-    out->slice_end = h->plan_se.data();
-    out->first_row = h->plan_first.data();
-    out->rows = h->plan_rows.data();
-    out->changed = h->plan_changed.data();
-    if (timer_watermark) *timer_watermark = h->plan_wm;
+    h->snap.plan.point(out);
+    if (timer_watermark) *timer_watermark = h->snap.plan_wm;
     return FG_OK;
 }
 
 int fg_snapshot_state_select_async(fg_handle* h, const uint8_t* want, int64_t n) {
-    if (!h) return FG_EINVAL;
-    HIPCHK(h, hipSetDevice(h->device));
-    if (h->snap_pending) return h->fail(FG_ESTATE, "an asynchronous snapshot is not collected yet (fg_snapshot_state_wait)");
-    return snapshot_select(h, want, n);
+    return snapshot_select(h, "fg_snapshot_state_select_async", want, n);
 }
 
 int fg_snapshot_state_select(fg_handle* h, const uint8_t* want, int64_t n, fg_state_rows* out, int64_t* timer_watermark) {
-    if (!h || !out) return FG_EINVAL;
-    if (int rc = fg_snapshot_state_select_async(h, want, n)) return rc;
+    if (!out) return FG_EINVAL;
+    if (int rc = snapshot_select(h, "fg_snapshot_state_select", want, n)) return rc;
     return snapshot_end(h, out, timer_watermark);
 }
 
@@ -4921,14 +4891,14 @@ static int restore_images(fg_handle* h, const char* fn, const fg_state_rows* ima
 
 int fg_restore(fg_handle* h, const fg_state_rows* in, int64_t timer_watermark) {
     if (!h || !in) return FG_EINVAL;
-    h->plan_valid = false;
+    h->snap.plan_valid = false;
     return restore_images(h, "fg_restore", in, 1, FG_HOST, false, 0, timer_watermark, nullptr);
 }
 
 int fg_restore_range(fg_handle* h, const fg_state_rows* images, int32_t n_images, int32_t location, int32_t key_hash,
                      int64_t timer_watermark, fg_restore_info* info) {
     if (!h) return FG_EINVAL;
-    h->plan_valid = false;
+    h->snap.plan_valid = false;
     if (n_images < 0 || (n_images > 0 && !images))
         return h->fail(FG_EINVAL, "fg_restore_range: %d images", n_images);
     if (location != FG_HOST && location != FG_DEVICE)
@@ -4971,7 +4941,7 @@ int fg_synchronize(fg_handle* h) {
 
 int fg_reset(fg_handle* h) {
     if (!h) return FG_EINVAL;
-    h->plan_valid = false;
+    h->snap.plan_valid = false;
     HIPCHK(h, hipSetDevice(h->device));
     if (int rc0 = settle_pending(h)) return rc0;
     int rc = sync(h);

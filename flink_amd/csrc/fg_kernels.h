@@ -332,22 +332,7 @@ struct AccColumns {
     int64_t* v2;
 };
 
-struct ExportParams {
-    TableRef t;
-    const uint64_t* region_off;  // [P] exclusive prefix of counts
-    int64_t slice_end;
-    int64_t* out_key;
-    int64_t* out_slice;
-    int64_t* out_cnt_star;
-    int64_t* out_cnt_val;
-    int64_t* out_sum;
-    int64_t* out_v1;             // multi-value operator: value slots 1 and 2
-    int64_t* out_v2;
-    int32_t mv;
-    int32_t pad;
-};
-
-// Selective image (k_export_sel): one descriptor per selected table, ascending by slice; the rows
+// Checkpoint image (k_export_sel): one descriptor per selected table, ascending by slice; the rows
 // of (table t, region r) go to image rows row_base + [off[r], off[r + 1]), off = region_off +
 // t * (regions + 1): the exclusive prefix of the table's region counts, regions + 1 entries.
 struct ExportSelTable {
@@ -434,7 +419,6 @@ hipError_t launch_hist_columns(uint32_t* hist, uint32_t* totals, int32_t F, int3
 hipError_t launch_merge(const MergeParams& p, int32_t workgroups, hipStream_t s);
 // fire one window straight from a single slice table (no combine): p's emit fields
 hipError_t launch_emit_table(const MergeParams& p, const TableRef& t, hipStream_t s);
-hipError_t launch_export(const ExportParams& p, int32_t regions, hipStream_t s);
 // region split: the table `src` at old_bits -> `dst` at old_bits + shift (each region's
 // entries go to its 2^shift child regions by the next bits of their key mix)
 // a narrow table rewritten wide in place (regions 2^bits)

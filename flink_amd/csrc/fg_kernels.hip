@@ -12,9 +12,8 @@
 //                                      AggCombiner.combine, combines/AggCombiner.java:76-115)
 //                                      and/or emits fired rows (fireWindow + mergeSlices,
 //                                      processors/SliceSharedWindowAggProcessor.java:64-118)
-//   k_export                           checkpoint image of the resident state
-//   k_export_sel                       selective checkpoint image: the tables of a descriptor array
-//                                      (the slices a caller selected) in one launch
+//   k_export_sel                       checkpoint image: the tables of a descriptor array (every
+//                                      resident slice, or those a caller selected) in one launch
 //   k_key_groups / k_owner_*           KeyGroupRangeAssignment routing for the key-group exchange
 //   k_rr_*                             rescale restore: checkpoint images filtered by key-group range
 //                                      and grouped by (slice, region) for the merge
@@ -2853,38 +2852,12 @@ hipError_t launch_heavy_chunks(const HeavyPlan& hp, int32_t workgroups, hipStrea
 // ----------------------------------------------------------------------------------------
 // export (checkpoint image)
 // ----------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_export(ExportParams p) {
-    const int r = blockIdx.x;
-    const uint32_t n = p.t.counts[r];
-    const int cap = table_cap(p.mv);
-    const auto base = gbl(p.t.base + (int64_t)r * table_cols(p.mv) * cap);
-    const bool nar = p.t.narrow != 0;
-    const uint64_t o = p.region_off[r];
-    for (uint32_t i = threadIdx.x; i < n; i += 256) {
-        const int64_t cs = tab_cs(base, cap, i, nar), cn = tab_cn(base, cap, i, nar);
-        p.out_key[o + i] = nar ? (int64_t)tab_key32(base, cap, i, nar) : key_of(base[i]);
-        p.out_slice[o + i] = p.slice_end;
-        p.out_cnt_star[o + i] = cs;
-        p.out_cnt_val[o + i] = cs - cn;
-        p.out_sum[o + i] = tab_v(base, cap, i, nar);
-        if (p.mv) {
-            p.out_v1[o + i] = base[4 * cap + i];
-            p.out_v2[o + i] = base[5 * cap + i];
-        }
-    }
-}
-
-hipError_t launch_export(const ExportParams& p, int32_t regions, hipStream_t s) {
-    fg_launch(k_export, dim3(regions), dim3(256), 0, s, p);
-    return hipGetLastError();
-}
-
-// selective image: the tables of one descriptor array in one launch, grid (region, selected table).
-// A workgroup walks its region as k_export does (consecutive lanes on consecutive entries of every
-// column); the layout flag and the counts are the table's own, the row offsets 64-bit. The entries
-// written are bounded by the offsets' span, so that a count the host did not plan for cannot write
-// past the image. WITH_CV = false: no selected table counts NULL values, the cnt_val column is the
-// cnt_star column and is not written.
+// the tables of one descriptor array (every resident slice, or a select's) in one launch, grid
+// (region, selected table). A workgroup walks its region with consecutive lanes on consecutive
+// entries of every column; the layout flag and the counts are the table's own, the row offsets
+// 64-bit. The entries written are bounded by the offsets' span, so that a count the host did not
+// plan for cannot write past the image. WITH_CV = false: no selected table counts NULL values, the
+// cnt_val column is the cnt_star column and is not written.
 template <bool WITH_CV>
 __global__ __launch_bounds__(256) void k_export_sel(ExportSelParams p) {
     const int r = blockIdx.x;

@@ -343,7 +343,14 @@ int  fg_snapshot_state(fg_handle* h, fg_state_rows* out, int64_t* timer_watermar
  * fg_snapshot_state layout, valid until the next snapshot call) once the copy has completed.
  * One snapshot at a time: fg_snapshot_state[_async] fails with FG_ESTATE while one is not
  * collected. fg_snapshot_state is _async + _wait. An image of an operator that never saw a NULL
- * value may return the same column for cnt_star and cnt_val (they are equal). */
+ * value may return the same column for cnt_star and cnt_val (they are equal).
+ * A full image is fg_snapshot_plan + fg_snapshot_state_select_async with every slice selected (one
+ * export launch) and shares the select's limits: at most 65,535 resident slices and fewer than 2^32
+ * rows (over 130 GB of image columns). Beyond either the call returns FG_EINVAL after the staged
+ * records are flushed and before a row is exported or copied; the handle stays usable. A caller's
+ * earlier fg_snapshot_plan is invalid from the call on, and no plan is valid after it.
+ * fg_kernel_stats: a full image counts under "export" (one launch per image with rows, records =
+ * the image's rows), a selective one under "export_select". */
 int  fg_snapshot_state_async(fg_handle* h);
 int  fg_snapshot_state_wait(fg_handle* h, fg_state_rows* out, int64_t* timer_watermark);
 /* The slices of the image the last fg_snapshot_state / fg_snapshot_state_wait returned (ABI 16):
@@ -413,7 +420,8 @@ int  fg_snapshot_key_groups(fg_handle* h, fg_image_key_groups* out);
  *    every other call on the handle invalidates it, and a select consumes it. The image is therefore
  *    the state as of the plan.
  *  - FG_EINVAL before any device work (the handle stays usable, the plan stays valid): n differs from
- *    the plan's n; want is NULL with n > 0; 2^32 or more selected rows.
+ *    the plan's n; want is NULL with n > 0; 2^32 or more selected rows; more than 65,535 selected
+ *    slices.
  *  - The image holds exactly the rows a full image holds for the selected slices (per slice the same
  *    multiset), grouped by slice, ascending, compact from row 0. After the wait fg_snapshot_slices
  *    describes that image: only the selected slices, first_row the compact prefix, changed as planned.

@@ -1,8 +1,11 @@
 """Selective snapshot images (fg_snapshot_plan -> mask -> fg_snapshot_state_select[_async]): the
 engine exports and copies only the slices the caller asks for, in one k_export_sel launch.
 
-The reference of every check is the full image (snapshot_state, the per-table k_export) taken on the
-same handle right after the select: the state is the same, only the `changed` flags differ. Values are
+The reference of most checks is the full image (snapshot_state) taken on the same handle right after
+the select: the state is the same, only the `changed` flags differ. The full image is a select of
+every slice through the same kernel, so these comparisons check the mask, the compaction and the
+bookkeeping, not the kernel; the kernel's rows are pinned against images built in numpy alone
+(test_narrow_and_wide_tables_against_numpy here, assert_state_is in test_gpu_restore_range). Values are
 BIGINT wherever bits are compared (and every (key, slice) is one row of an image, so DOUBLE bits of
 one handle's two images are equal too). The end-to-end cases drive the shim's policy
 (keyed_state.wanted_slices / write_delta) against write_image and write_image_full."""
@@ -101,9 +104,10 @@ def test_subset_mask_first_last_and_a_middle_slice():
 
 # ---- 3: table layouts in one launch ---------------------------------------------------------------
 
-def test_narrow_tables_next_to_wide_ones():
+def narrow_and_wide_op():
     """in-order batches of 32-bit keys without NULLs flush from their tiles (tables with 16-B
-    entries); then a batch with keys beyond 32 bits in later slices only (wide tables)"""
+    entries); then a batch with keys beyond 32 bits in later slices only (wide tables). Nothing fires
+    (no watermark). Returns the open operator and the stream as it was fed."""
     import flink_amd as F
     n, keys = 120_000, 20_000
     key, ts, val, _ = make_stream(n, keys, "i64", rate_per_ms=30)   # in order, 4 s
@@ -124,6 +128,15 @@ def test_narrow_tables_next_to_wide_ones():
         op.prepare_snapshot_pre_barrier()
         ks1 = op.kernel_stats()
         assert ks1["tile_flush"]["launches"] == ks0["tile_flush"]["launches"], "the wide batch was tile-staged"
+    except BaseException:
+        op.close()
+        raise
+    return op, np.concatenate([key[:cut], k2]), ts, val
+
+
+def test_narrow_tables_next_to_wide_ones():
+    op, _, _, _ = narrow_and_wide_op()
+    try:
         r = select_and_full(op, lambda p: np.ones(len(p["slice_end"])))
         check_select(*r, ctx="narrow + wide, all")
         assert len(r[0]["slice_end"]) >= 4 and (np.abs(r[2]["key"]) > (1 << 33)).any()
@@ -131,6 +144,36 @@ def test_narrow_tables_next_to_wide_ones():
         check_select(*r, ctx="narrow + wide, every other")
     finally:
         op.close()
+
+
+def test_narrow_and_wide_tables_against_numpy():
+    """the images of narrow_and_wide_op's state against one built from its stream in numpy alone: a
+    row per (key, slice), cnt_star = cnt_val = the records (no NULLs), sum their int64 sum. The full
+    image, the all-ones select and the every-other-slice select."""
+    op, key, ts, val = narrow_and_wide_op()
+    try:
+        full, _ = op.snapshot_state()
+        plan, _ = op.snapshot_plan()
+        assert len(plan["slice_end"]) == 4, plan["slice_end"]
+        ones, _ = op.snapshot_state_select(np.ones(4, dtype=np.uint8))
+        op.snapshot_plan()
+        other, _ = op.snapshot_state_select(np.array([1, 0, 1, 0], dtype=np.uint8))
+        other_sl = op.snapshot_slices()
+    finally:
+        op.close()
+    assert (np.diff(ts) >= 0).all()   # in order: nothing is late
+    se = (ts // 1000 + 1) * 1000
+    order = np.lexsort((key, se))
+    k, s, v = key[order], se[order], val[order]
+    first = np.flatnonzero(np.r_[True, (k[1:] != k[:-1]) | (s[1:] != s[:-1])])
+    cnt = np.diff(np.r_[first, len(k)]).astype(np.int64)
+    want = {"key": k[first], "slice_end": s[first], "cnt_star": cnt, "cnt_val": cnt, "sum": np.add.reduceat(v, first)}
+    ends = np.unique(se)
+    assert len(ends) == 4 and len(first) == 65_893 and int((np.abs(want["key"]) > (1 << 33)).sum()) == 5_167
+    assert_same_rows(want, full, "full image vs numpy")
+    assert_same_rows(want, ones, "all-ones select vs numpy")
+    assert np.array_equal(other_sl["slice_end"], ends[::2])
+    assert_same_rows(restrict(want, ends[::2]), other, "every-other-slice select vs numpy")
 
 
 def test_min_max_columns_and_null_counts():
@@ -402,11 +445,47 @@ def test_a_select_is_one_launch():
         assert after["export_select"]["launches"] - before["export_select"]["launches"] == 1
         assert after["export"]["launches"] == before["export"]["launches"]
         assert after["export_select"]["records"] - before["export_select"]["records"] == len(img["key"]) > 0
-        op.snapshot_state()
+        whole, _ = op.snapshot_state()
         op.synchronize()
         full = op.kernel_stats()
-        assert full["export"]["launches"] - after["export"]["launches"] == n   # the full image: a launch per table
+        assert full["export"]["launches"] - after["export"]["launches"] == 1   # the full image: one launch too
+        assert full["export"]["records"] - after["export"]["records"] == len(whole["key"]) > len(img["key"])
         assert full["export_select"]["launches"] == after["export_select"]["launches"]
+    finally:
+        op.close()
+
+
+def test_full_image_of_a_fresh_handle_and_of_changed_slices():
+    """the full path's two ends: nothing resident (an empty image, no launch), and every slice changed
+    (reported as the plan just before reports it, cleared by the image)"""
+    op = mk(OPS["hop_i64_big"], kernel_timing=True)
+    try:
+        before = op.kernel_stats()
+        img, _ = op.snapshot_state()
+        op.synchronize()
+        assert len(img["key"]) == 0 and len(op.snapshot_slices()["slice_end"]) == 0
+        assert op.kernel_stats()["export"]["launches"] == before["export"]["launches"]
+    finally:
+        op.close()
+    spec = OPS["hop_i64_big"]
+    key, ts, val, _ = make_stream(60000, 3000, spec["vt"], jitter_ms=300, rate_per_ms=10, **spec["gen"])   # mid_stream's
+    op = mk(spec)
+    try:
+        for lo, hi, wm in list(batches_with_watermarks(60000, 10000, ts, 1500))[:3]:
+            op.process_batch(key[lo:hi], ts[lo:hi], val[lo:hi])
+            op.process_watermark(wm)
+        plan, _ = op.snapshot_plan()
+        first, _ = op.snapshot_state()
+        sl = op.snapshot_slices()
+        assert len(plan["slice_end"]) >= 3 and plan["changed"].all()
+        for c in ("slice_end", "first_row", "rows", "changed"):
+            assert np.array_equal(sl[c], plan[c]), c
+        again, _ = op.snapshot_plan()
+        assert np.array_equal(again["slice_end"], plan["slice_end"]) and not again["changed"].any()
+        second, _ = op.snapshot_state()
+        assert len(second["key"]) == int(plan["rows"].sum()) > 0
+        assert_same_rows(first, second, "a second full image")
+        assert not op.snapshot_slices()["changed"].any()
     finally:
         op.close()
 
