@@ -4175,8 +4175,9 @@ int run_selftest(int device, char* msg, size_t cap_msg) {
 // the item like a full table: nothing is written or emitted and its regions are redone.
 // m.emit = 0: a flush (the table written, no rows).
 // HOT (a skewed pass's split fire, SUM-family value ops): the insert pre-combines a wave's records of
-// a hot key; the plain fire keeps the one-probe-loop-per-record insert (A/B, round 5: 0.89 vs 1.08
-// ms per 100M records for the branch-free insert with a dummy slot)
+// a hot key; the split and table fires keep the one-probe-loop-per-record insert (A/B, round 5: 0.89
+// vs 1.08 ms per 100M records for the branch-free insert with a dummy slot); the plain fire without
+// tables settles home-bucket hits in line and queues the misses per wave (insert_plain, QUEUE)
 // SM: 0 the plain fire (no split code: the split and merge paths cost it 4 spilled VGPRs, round 5),
 // 1 a split fire's launches (chunk items, then the merge launch), 2 chunk items with HOT
 template <int VTC, bool TAB, int SM>   // TAB: source / destination tables (compiled out of the plain fire)
@@ -4195,7 +4196,10 @@ __global__ __launch_bounds__(kTileFireThreads) void k_tile_fire(TileFire fa) {
     __shared__ __attribute__((aligned(16))) uint8_t s_fm[W][kTileWin];
     __shared__ uint32_t s_dl[W][kTileGroup];
     __shared__ uint32_t s_grp[kRounds * W];
-    __shared__ uint16_t s_map[S + 1];
+    // (during the inserts: the waves' miss queues, kQueueCap records {u64 value bits}[], {int32 key}[] each)
+    __shared__ __attribute__((aligned(16))) uint16_t s_map[S + 1];
+    constexpr int kQueueBytes = 2 * S / W, kQueueCap = kQueueBytes / 12;
+    static_assert(kQueueBytes % 8 == 0 && kQueueCap >= 64, "a wave's miss queue takes a whole record step");
     __shared__ unsigned int s_flags;
     __shared__ uint32_t s_total;
     __shared__ unsigned long long s_out_base;
@@ -4505,9 +4509,36 @@ __global__ __launch_bounds__(kTileFireThreads) void k_tile_fire(TileFire fa) {
                 }
             }
         } else if (live) {
-            // one window's records into the table, one probe loop per record (the plain fire)
+            // one window's records into the table
             // (FULL: a whole window, every lane's records present; RETRY: the region filter --
             // compile-time tags, so the common case's loop carries neither per-record test)
+            // QUEUE (the plain fire without tables): a record whose key sits in its home bucket
+            // (five lanes in six: ~10 % of the records are a key's first of the fire, ~6 % of the
+            // keys overflow their home bucket) is settled in line from the bucket copy read before
+            // the inserts, no loop and no CAS -- a hit in a stale copy is a
+            // valid slot, keys are never removed. The others are queued per wave {value, key} in
+            // the rank -> slot map's LDS (idle until the barrier after the inserts) and resolved
+            // 64 at a time by slot_of, so the CAS / reload / probe-on round trips are paid by full
+            // waves and not once per record step by the few lanes that need them. The table and
+            // split fires keep one probe loop per record: with the queue they spill 8-12 VGPRs.
+            constexpr bool QUEUE = !TAB && SM == 0;
+            uint32_t qn = 0;   // the wave's queued records (wave-uniform)
+            unsigned long long* const q_val = reinterpret_cast<unsigned long long*>(s_map) + wave * (kQueueBytes / 8);
+            int32_t* const q_key = reinterpret_cast<int32_t*>(q_val + kQueueCap);
+            // the queue's last c (<= 64) records into the table
+            auto drain = [&](uint32_t c) {
+                wave_lds_sync();   // (the appends of other lanes)
+                qn -= c;
+                if ((uint32_t)lane < c) {
+                    const int sl = slot_of(q_key[qn + lane]);
+                    if (sl < 0) {
+                        full = true;
+                    } else {
+                        atomicAdd(&t_cs[sl], 1u);
+                        lds_val(&t_v[sl], (int64_t)q_val[qn + lane], vt, true);
+                    }
+                }
+            };
             auto insert_plain = [&](auto FULL, auto RETRY, const int32_t (&kr)[kTileRpl], const int64_t (&vr)[kTileRpl],
                                     uint32_t nrec) {
 #if defined(FG_DIAG_FIRE) && (FG_DIAG_FIRE & 2)   // (diagnostic: no inserts, the records consumed)
@@ -4525,47 +4556,77 @@ __global__ __launch_bounds__(kTileFireThreads) void k_tile_fire(TileFire fa) {
                 }
 #pragma unroll
                 for (int u = 0; u < kTileRpl; u++) {
-                    if (!decltype(FULL)::value && lane + 64 * u >= nrec) continue;
-                    const int32_t key = kr[u];
-                    if (decltype(RETRY)::value && retry &&
-                        (int)((uint64_t)mix_of((int64_t)key) >> (64 - p.region_bits)) != r_lo)
-                        continue;
-                    int sl = -1;
-                    if (key == kEmpty32) {
-                        sl = S;
-                    } else {
-                        uint32_t home = hm[u];
-                        int4 q4 = bq[u];
-                        for (int probe = 0; probe < S / 4; probe++) {
-                            const int32_t qq[4] = {q4.x, q4.y, q4.z, q4.w};
-                            int hit = -1, emp = -1;
+                    if constexpr (!QUEUE) {   // one probe loop per record
+                        if (!decltype(FULL)::value && lane + 64 * u >= nrec) continue;
+                        const int32_t key = kr[u];
+                        if (decltype(RETRY)::value && retry &&
+                            (int)((uint64_t)mix_of((int64_t)key) >> (64 - p.region_bits)) != r_lo)
+                            continue;
+                        int sl = -1;
+                        if (key == kEmpty32) {
+                            sl = S;
+                        } else {
+                            uint32_t home = hm[u];
+                            int4 q4 = bq[u];
+                            for (int probe = 0; probe < S / 4; probe++) {
+                                const int32_t qq[4] = {q4.x, q4.y, q4.z, q4.w};
+                                int hit = -1, emp = -1;
 #pragma unroll
-                            for (int z = 3; z >= 0; z--) {
-                                if (qq[z] == key) hit = z;
-                                if (qq[z] == kEmpty32) emp = z;
-                            }
-                            if (hit >= 0 && (emp < 0 || hit < emp)) {
-                                sl = (int)home + hit;
-                                break;
-                            }
-                            if (emp >= 0) {
-                                const int old = atomicCAS(&t_key[home + emp], kEmpty32, key);
-                                if (old == kEmpty32 || old == key) {
-                                    sl = (int)home + emp;
+                                for (int z = 3; z >= 0; z--) {
+                                    if (qq[z] == key) hit = z;
+                                    if (qq[z] == kEmpty32) emp = z;
+                                }
+                                if (hit >= 0 && (emp < 0 || hit < emp)) {
+                                    sl = (int)home + hit;
                                     break;
                                 }
-                            } else {
-                                home = (home + 4) & (S - 1);
+                                if (emp >= 0) {
+                                    const int old = atomicCAS(&t_key[home + emp], kEmpty32, key);
+                                    if (old == kEmpty32 || old == key) {
+                                        sl = (int)home + emp;
+                                        break;
+                                    }
+                                } else {
+                                    home = (home + 4) & (S - 1);
+                                }
+                                q4 = *reinterpret_cast<const int4*>(&t_key[home]);
                             }
-                            q4 = *reinterpret_cast<const int4*>(&t_key[home]);
                         }
+                        if (sl < 0) {
+                            full = true;
+                            continue;
+                        }
+                        atomicAdd(&t_cs[sl], 1u);
+                        lds_val(&t_v[sl], vr[u], vt, true);
+                    } else {   // settled from the prefetched home bucket, or queued
+                        const int32_t key = kr[u];
+                        bool valid = decltype(FULL)::value || lane + 64 * u < nrec;
+                        if (decltype(RETRY)::value && retry)
+                            valid = valid && (int)((uint64_t)mix_of((int64_t)key) >> (64 - p.region_bits)) == r_lo;
+                        const int4 q4 = bq[u];
+                        int z = q4.w == key ? 3 : -1;
+                        z = q4.z == key ? 2 : z;
+                        z = q4.y == key ? 1 : z;
+                        z = q4.x == key ? 0 : z;
+                        int sl = z >= 0 ? (int)hm[u] + z : -1;
+                        sl = key == kEmpty32 ? S : sl;   // (a home bucket never holds the sentinel as a key)
+                        if (valid && sl >= 0) {
+                            atomicAdd(&t_cs[sl], 1u);
+                            lds_val(&t_v[sl], vr[u], vt, true);
+                        }
+                        const bool miss = valid && sl < 0;
+                        const uint64_t bal = __ballot(miss);
+                        if (bal == 0) continue;   // (uniform)
+                        const uint32_t m = (uint32_t)__popcll(bal);
+                        if (qn + m > (uint32_t)kQueueCap) drain(qn);   // (qn < 64 here: room for a whole step)
+                        if (miss) {
+                            const uint32_t at = qn + (uint32_t)__popcll(bal & ((1ull << lane) - 1));
+                            q_val[at] = (unsigned long long)vr[u];
+                            q_key[at] = key;
+                        }
+                        qn += m;
+                        if (qn >= 64u) drain(64u);
                     }
-                    if (sl < 0) {
-                        full = true;
-                        continue;
-                    }
-                    atomicAdd(&t_cs[sl], 1u);
-                    lds_val(&t_v[sl], vr[u], vt, true);
                 }
             };
             // the split fire's insert. A bucket fills in slot order and keys are never
@@ -4715,6 +4776,10 @@ __global__ __launch_bounds__(kTileFireThreads) void k_tile_fire(TileFire fa) {
                     FSTAMP(3);
                 }
                 if (__ballot(w.bad) != 0 && lane == 0) atomicOr(p.overflow, 8u);
+            }
+            if constexpr (QUEUE) {   // what the queue still holds, before the barrier that ends the inserts
+                while (qn != 0) drain(qn < 64u ? qn : 64u);
+                FSTAMP(3);
             }
         }
         if (full) atomicOr(&s_flags, 4u);
