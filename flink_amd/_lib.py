@@ -99,6 +99,11 @@ class FgImageKeyGroups(C.Structure):
     _fields_ = [("n_slices", C.c_int64), ("max_parallelism", C.c_int32), ("first_row", C.c_void_p)]
 
 
+class FgRowRuns(C.Structure):
+    _fields_ = [("n", C.c_int64), ("window_start", C.c_void_p), ("window_end", C.c_void_p), ("rowtime", C.c_void_p),
+                ("first_row", C.c_void_p), ("rows", C.c_void_p)]
+
+
 class FgStats(C.Structure):
     _fields_ = [(n, C.c_int64) for n in (
         "records_in", "records_staged", "late_dropped", "rows_fired", "flushes", "live_slices",
@@ -129,6 +134,7 @@ EXPORTS = (
     "fg_snapshot_state_async", "fg_snapshot_state_wait", "fg_snapshot_slices", "fg_selftest", "fg_restore", "fg_restore_range", "fg_late_dropped", "fg_get_stats", "fg_synchronize", "fg_reset", "fg_kernel_stats", "fg_set_kernel_timing",
     "fg_set_snapshot_grouping", "fg_snapshot_key_groups",
     "fg_snapshot_plan", "fg_snapshot_state_select_async", "fg_snapshot_state_select",
+    "fg_set_fired_runs", "fg_fired_runs",
     "fg_stream",
     "fg_last_error", "fg_close", "fg_key_groups", "fg_partition_by_owner", "fg_partition_columns_by_owner",
     "fg_abi_version", "fg_key_dict_open", "fg_key_dict_intern", "fg_key_dict_intern_async",
@@ -257,6 +263,12 @@ def load():
     L.fg_snapshot_state_select.argtypes = [P, P, C.c_int64, C.POINTER(FgStateRows), C.POINTER(C.c_int64)]
     for fn in ("fg_snapshot_plan", "fg_snapshot_state_select_async", "fg_snapshot_state_select"):
         getattr(L, fn).restype = C.c_int
+    # (hasattr: a variant library built from an older tree, FLINKGPU_LIB in scripts/ab_libs.sh, lacks
+    # them; asking it for run mode raises AttributeError, every other call works)
+    if hasattr(L, "fg_set_fired_runs"):
+        L.fg_set_fired_runs.argtypes = [P, C.c_int32]
+        L.fg_fired_runs.argtypes = [P, C.POINTER(FgRowRuns)]
+        L.fg_set_fired_runs.restype = L.fg_fired_runs.restype = C.c_int
     L.fg_selftest.argtypes = [C.c_int32, C.c_char_p, C.c_int32]
     L.fg_selftest.restype = C.c_int
     L.fg_comm_bytes_sent.argtypes = [P]

@@ -457,6 +457,21 @@ struct fg_handle {
     DevBuf o_agg[FG_MAX_AGGS];
     HostBuf h_key, h_ws, h_we, h_null, h_rt;
     HostBuf h_agg[FG_MAX_AGGS];
+    // Run mode (fg_set_fired_runs): the rows carry no window columns (o_ws / o_we / o_rt and their
+    // host mirrors stay unallocated); `runs` is the window of every emitting launch since the
+    // output buffers were last empty, adjacent equal windows folded (run_note, from fill_emit).
+    // Run r < runs.size() - 1 ends at the fired-row count k_run_mark stored into run_slot(r) when
+    // the next window's first launch was queued, the last run at out_n. The slots are coherent
+    // host memory in fixed chunks (never moved: a queued mark keeps its address).
+    bool fired_runs = false;
+    bool run_fail = false;   // a mark could not be queued: the directory is unknown
+    struct RunWin {
+        int64_t wstart, wend;
+    };
+    std::vector<RunWin> runs;
+    std::vector<std::unique_ptr<HostBuf>> run_end;
+    // the directory of the rows the last call returned (fg_fired_runs)
+    std::vector<int64_t> rd_ws, rd_we, rd_rt, rd_first, rd_rows;
 
     // snapshot image
     DevBuf s_key, s_slice, s_cs, s_cv, s_sum, s_off, s_v1, s_v2;
@@ -1143,6 +1158,74 @@ struct FireRange {   // windows whose timers fire in (prev, wm]
     int64_t prev, wm;
 };
 
+// ---- run mode: fired rows as runs (fg_set_fired_runs) ------------------
+constexpr size_t kRunChunk = 512;   // run-end words per coherent host chunk
+unsigned long long* run_slot(const fg_handle* h, size_t r) {
+    return h->run_end[r / kRunChunk]->as<unsigned long long>() + r % kRunChunk;
+}
+// The next emitting launch fires window [wstart, wend): when that is not the open run's window,
+// the open run ends at the fired-row count the stream has reached by then -- one k_run_mark,
+// queued here, ahead of the launch. (Called as the launch's parameters are filled, after
+// reset_out_count re-based the counter; a launch that emits nothing leaves an empty run, which
+// the directory drops.)
+void run_note(fg_handle* h, int64_t wstart, int64_t wend) {
+    if (!h->runs.empty() && h->runs.back().wend == wend) return;
+    if (!h->runs.empty()) {
+        const size_t r = h->runs.size() - 1;
+        while (h->run_end.size() * kRunChunk <= r) {
+            std::unique_ptr<HostBuf> c(new HostBuf());
+            if (c->ensure(8 * kRunChunk, hipHostMallocCoherent) != hipSuccess) {
+                h->run_fail = true;
+                return;
+            }
+            h->run_end.push_back(std::move(c));
+        }
+        const unsigned long long* count = reinterpret_cast<unsigned long long*>(h->scalars.as<char>() + 8);
+        if (launch_run_mark(count, run_slot(h, r), h->stream) != hipSuccess) {
+            h->run_fail = true;
+            return;
+        }
+    }
+    h->runs.push_back(fg_handle::RunWin{wstart, wend});
+}
+void runs_clear(fg_handle* h) {
+    h->runs.clear();
+    h->run_fail = false;
+}
+// The directory of the rows [0, out_n) a call returns, from the marks (all of them stored: the
+// call synchronized with, or completed, the last fire): empty runs dropped, neighbours of one
+// window folded.
+int runs_directory(fg_handle* h) {
+    h->rd_ws.clear();
+    h->rd_we.clear();
+    h->rd_rt.clear();
+    h->rd_first.clear();
+    h->rd_rows.clear();
+    if (!h->fired_runs) return FG_OK;
+    if (h->run_fail) return h->fail(FG_EDEVICE, "fired runs: a run mark could not be queued");
+    int64_t prev = 0;
+    for (size_t r = 0; r < h->runs.size(); r++) {
+        const int64_t end = r + 1 < h->runs.size() ? (int64_t)*(const volatile unsigned long long*)run_slot(h, r) : h->out_n;
+        if (end < prev || end > h->out_n)
+            return h->fail(FG_EDEVICE, "internal: fired run %zu ends at row %lld (previous end %lld, %lld rows)", r,
+                           (long long)end, (long long)prev, (long long)h->out_n);
+        if (end == prev) continue;
+        if (!h->rd_we.empty() && h->rd_we.back() == h->runs[r].wend) {
+            h->rd_rows.back() += end - prev;
+        } else {
+            h->rd_ws.push_back(h->runs[r].wstart);
+            h->rd_we.push_back(h->runs[r].wend);
+            h->rd_rt.push_back(jsub(h->runs[r].wend, 1));
+            h->rd_first.push_back(prev);
+            h->rd_rows.push_back(end - prev);
+        }
+        prev = end;
+    }
+    if (prev != h->out_n)
+        return h->fail(FG_EDEVICE, "internal: fired runs cover %lld of %lld rows", (long long)prev, (long long)h->out_n);
+    return FG_OK;
+}
+
 void fill_emit(fg_handle* h, MergeParams& p, int64_t wend) {
     p.emit = 1;
     // local phase: the emitted "window" is the slice itself (LocalAggCombiner emits
@@ -1156,11 +1239,18 @@ void fill_emit(fg_handle* h, MergeParams& p, int64_t wend) {
         p.out_agg[a] = h->o_agg[a].as<int64_t>();
     }
     p.out_key = h->o_key.as<int64_t>();
+    p.out_null = h->o_null.as<uint8_t>();
+    p.out_cap = h->out_cap;
+    if (h->fired_runs) {   // the window goes into the run directory, not into the rows
+        p.out_ws = nullptr;
+        p.out_we = nullptr;
+        p.out_rowtime = nullptr;
+        run_note(h, p.wstart, wend);
+        return;
+    }
     p.out_ws = h->o_ws.as<int64_t>();
     p.out_we = h->o_we.as<int64_t>();
-    p.out_null = h->o_null.as<uint8_t>();
     p.out_rowtime = h->cfg.mode == FG_MODE_DATASTREAM ? h->o_rt.as<int64_t>() : nullptr;
-    p.out_cap = h->out_cap;
 }
 
 bool staged_any(const fg_handle* h) {
@@ -1823,10 +1913,12 @@ int ensure_out(fg_handle* h, int64_t need) {
     int64_t nc = std::max<int64_t>(need, h->out_cap + h->out_cap / 2);
     nc = std::max<int64_t>(nc, 1024);
     HIPCHK(h, h->o_key.ensure(8 * nc, h->stream, true));
-    HIPCHK(h, h->o_ws.ensure(8 * nc, h->stream, true));
-    HIPCHK(h, h->o_we.ensure(8 * nc, h->stream, true));
     HIPCHK(h, h->o_null.ensure(nc, h->stream, true));
-    if (h->cfg.mode == FG_MODE_DATASTREAM) HIPCHK(h, h->o_rt.ensure(8 * nc, h->stream, true));
+    if (!h->fired_runs) {   // (run mode: no window columns)
+        HIPCHK(h, h->o_ws.ensure(8 * nc, h->stream, true));
+        HIPCHK(h, h->o_we.ensure(8 * nc, h->stream, true));
+        if (h->cfg.mode == FG_MODE_DATASTREAM) HIPCHK(h, h->o_rt.ensure(8 * nc, h->stream, true));
+    }
     for (int a = 0; a < h->cfg.num_aggs; a++) HIPCHK(h, h->o_agg[a].ensure(8 * nc, h->stream, true));
     h->out_cap = nc;
     return FG_OK;
@@ -2315,29 +2407,34 @@ int refire(fg_handle* h, int64_t wm) {
 int copy_out_to_host(fg_handle* h, fg_rows* r) {
     const int64_t n = h->out_n;
     const size_t b8 = 8 * (size_t)std::max<int64_t>(n, 1);
+    const bool win = !h->fired_runs;   // (run mode: the window columns exist on neither side)
+    const bool rt = win && h->cfg.mode == FG_MODE_DATASTREAM;
     HIPCHK(h, h->h_key.ensure(b8));
-    HIPCHK(h, h->h_ws.ensure(b8));
-    HIPCHK(h, h->h_we.ensure(b8));
+    if (win) {
+        HIPCHK(h, h->h_ws.ensure(b8));
+        HIPCHK(h, h->h_we.ensure(b8));
+    }
     HIPCHK(h, h->h_null.ensure(std::max<int64_t>(n, 1)));
-    if (h->cfg.mode == FG_MODE_DATASTREAM) HIPCHK(h, h->h_rt.ensure(b8));
+    if (rt) HIPCHK(h, h->h_rt.ensure(b8));
     for (int a = 0; a < h->cfg.num_aggs; a++) HIPCHK(h, h->h_agg[a].ensure(b8));
     if (n > 0) {
         HIPCHK(h, hipMemcpyAsync(h->h_key.p, h->o_key.p, 8 * n, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->h_ws.p, h->o_ws.p, 8 * n, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->h_we.p, h->o_we.p, 8 * n, hipMemcpyDeviceToHost, h->stream));
+        if (win) {
+            HIPCHK(h, hipMemcpyAsync(h->h_ws.p, h->o_ws.p, 8 * n, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipMemcpyAsync(h->h_we.p, h->o_we.p, 8 * n, hipMemcpyDeviceToHost, h->stream));
+        }
         HIPCHK(h, hipMemcpyAsync(h->h_null.p, h->o_null.p, n, hipMemcpyDeviceToHost, h->stream));
-        if (h->cfg.mode == FG_MODE_DATASTREAM)
-            HIPCHK(h, hipMemcpyAsync(h->h_rt.p, h->o_rt.p, 8 * n, hipMemcpyDeviceToHost, h->stream));
+        if (rt) HIPCHK(h, hipMemcpyAsync(h->h_rt.p, h->o_rt.p, 8 * n, hipMemcpyDeviceToHost, h->stream));
         for (int a = 0; a < h->cfg.num_aggs; a++)
             HIPCHK(h, hipMemcpyAsync(h->h_agg[a].p, h->o_agg[a].p, 8 * n, hipMemcpyDeviceToHost, h->stream));
         int rc = sync(h);
         if (rc) return rc;
     }
     r->key = h->h_key.as<int64_t>();
-    r->window_start = h->h_ws.as<int64_t>();
-    r->window_end = h->h_we.as<int64_t>();
+    r->window_start = win ? h->h_ws.as<int64_t>() : nullptr;
+    r->window_end = win ? h->h_we.as<int64_t>() : nullptr;
     r->null_mask = h->h_null.as<uint8_t>();
-    r->rowtime = h->cfg.mode == FG_MODE_DATASTREAM ? h->h_rt.as<int64_t>() : nullptr;
+    r->rowtime = rt ? h->h_rt.as<int64_t>() : nullptr;
     for (int a = 0; a < h->cfg.num_aggs; a++) r->agg[a] = h->h_agg[a].as<int64_t>();
     return FG_OK;
 }
@@ -3997,6 +4094,7 @@ static int advance_progress(fg_handle* h, int64_t wm) {
     // rows of async advances not collected yet lead this advance's rows (an async advance appends
     // to them; a synchronous one returns them ahead of its own)
     h->adv_base = h->async_open ? h->out_n : 0;
+    if (h->adv_base == 0) runs_clear(h);   // (run mode: the output buffers start empty; else the runs go on)
     h->out_n = h->adv_base + h->late_rows;   // rows fired by late elements since the last advance come first
     h->pending_out = 0;
     h->out_count_reset = false;
@@ -4162,10 +4260,10 @@ static void device_rows(fg_handle* h, int32_t out_location, fg_rows* fired) {
     fired->num_aggs = h->cfg.num_aggs;
     fired->location = out_location;
     fired->key = h->o_key.as<int64_t>();
-    fired->window_start = h->o_ws.as<int64_t>();
-    fired->window_end = h->o_we.as<int64_t>();
+    fired->window_start = h->fired_runs ? nullptr : h->o_ws.as<int64_t>();
+    fired->window_end = h->fired_runs ? nullptr : h->o_we.as<int64_t>();
     fired->null_mask = h->o_null.as<uint8_t>();
-    fired->rowtime = h->cfg.mode == FG_MODE_DATASTREAM ? h->o_rt.as<int64_t>() : nullptr;
+    fired->rowtime = h->cfg.mode == FG_MODE_DATASTREAM && !h->fired_runs ? h->o_rt.as<int64_t>() : nullptr;
     for (int a = 0; a < h->cfg.num_aggs; a++) fired->agg[a] = h->o_agg[a].as<int64_t>();
 }
 
@@ -4174,8 +4272,12 @@ int fg_collect_fired_to(fg_handle* h, int32_t out_location, fg_rows* fired) {
     h->snap.plan_valid = false;
     HIPCHK(h, hipSetDevice(h->device));
     if (int rc = complete_fire(h)) return rc;
-    if (!h->async_open) h->out_n = 0;   // (every async advance since the last collect fired nothing)
+    if (!h->async_open) {   // (every async advance since the last collect fired nothing)
+        h->out_n = 0;
+        runs_clear(h);
+    }
     h->async_open = false;
+    if (int rc = runs_directory(h)) return rc;
     if (out_location == FG_HOST) {
         std::memset(fired, 0, sizeof *fired);
         fired->n = h->out_n;
@@ -4217,6 +4319,8 @@ int fg_advance_progress(fg_handle* h, int64_t wm, int32_t out_location, fg_rows*
     if (rc) return rc;
     h->rows_fired += h->out_n - h->adv_base;   // (the async rows were counted by their advances)
     h->async_open = false;
+    rc = runs_directory(h);
+    if (rc) return rc;
     if (fired) {
         std::memset(fired, 0, sizeof *fired);
         fired->n = h->out_n;
@@ -4524,6 +4628,54 @@ int fg_set_snapshot_grouping(fg_handle* h, int32_t key_hash) {
     return FG_OK;
 }
 
+int fg_set_fired_runs(fg_handle* h, int32_t on) {
+    if (!h) return FG_EINVAL;
+    h->snap.plan_valid = false;
+    const bool want = on != 0;
+    if (want && h->local)
+        return h->fail(FG_EINVAL, "fg_set_fired_runs: a FG_FLAG_LOCAL_PARTIALS handle's rows feed the exchange, which reads "
+                                  "window_end per row");
+    if (want && h->lateness > 0)
+        return h->fail(FG_EINVAL, "fg_set_fired_runs: allowed_lateness_ms > 0 fires rows whose window differs per row");
+    if (h->fire_pending) return h->fail(FG_ESTATE, "fg_set_fired_runs: a fire is pending (fg_collect_fired first)");
+    if (h->async_open || h->late_rows > 0)
+        return h->fail(FG_ESTATE, "fg_set_fired_runs: fired rows are not collected yet (fg_collect_fired first)");
+    if (want == h->fired_runs) return FG_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = sync(h)) return rc;   // (nothing in flight writes the columns released below)
+    h->fired_runs = want;
+    // the output columns are sized again by the next fire: with the window columns (off), or
+    // without them (on: released here, not allocated again)
+    h->out_cap = 0;
+    h->out_n = 0;
+    if (want) {
+        for (DevBuf* b : {&h->o_ws, &h->o_we, &h->o_rt}) {
+            DevBuf none;
+            b->swap(none);
+        }
+        for (HostBuf* b : {&h->h_ws, &h->h_we, &h->h_rt}) {
+            if (b->p) (void)hipHostFree(b->p);
+            b->p = nullptr;
+            b->bytes = 0;
+        }
+    }
+    runs_clear(h);
+    return runs_directory(h);
+}
+
+int fg_fired_runs(fg_handle* h, fg_row_runs* out) {
+    if (!h || !out) return FG_EINVAL;
+    h->snap.plan_valid = false;
+    if (!h->fired_runs) return h->fail(FG_ESTATE, "fg_fired_runs: run mode is off (fg_set_fired_runs)");
+    out->n = (int64_t)h->rd_we.size();
+    out->window_start = h->rd_ws.data();
+    out->window_end = h->rd_we.data();
+    out->rowtime = h->rd_rt.data();
+    out->first_row = h->rd_first.data();
+    out->rows = h->rd_rows.data();
+    return FG_OK;
+}
+
 int fg_snapshot_key_groups(fg_handle* h, fg_image_key_groups* out) {
     if (!h || !out) return FG_EINVAL;
     h->snap.plan_valid = false;
@@ -4634,6 +4786,14 @@ static int restore_finish(fg_handle* h, int64_t timer_watermark, bool was_empty)
     // records that arrive for them (refire)
     h->refire_hi = h->w.kind != TUMBLE && !h->local && !h->proctime ? timer_watermark : JMIN;
     h->refire_wm = JMIN;
+    // run mode: the directory of rows returned before the restore is gone; the runs of rows not
+    // yet collected stay with their rows
+    if (!h->async_open) runs_clear(h);
+    h->rd_ws.clear();
+    h->rd_we.clear();
+    h->rd_rt.clear();
+    h->rd_first.clear();
+    h->rd_rows.clear();
     if (h->lateness > 0) {
         // allowed lateness: windows that fired before the checkpoint keep only their cleanup
         // timers (WindowOperator.onEventTime fired their trigger timers); their slices stay
@@ -4963,6 +5123,8 @@ int fg_reset(fg_handle* h) {
     h->out_n = 0;
     h->pending_out = 0;
     h->async_open = false;
+    runs_clear(h);
+    (void)runs_directory(h);   // (no rows: an empty directory)
     h->re_new.clear();
     h->re_delta.clear();
     h->re_tmp.clear();

@@ -228,7 +228,7 @@ struct MergeParams {
     int32_t num_aggs;
     int32_t aggs[kMaxAggs];
     int64_t* out_key;
-    int64_t* out_ws;
+    int64_t* out_ws;           // out_ws, out_we: null in run mode (fg_set_fired_runs)
     int64_t* out_we;
     int64_t* out_agg[kMaxAggs];
     uint8_t* out_null;
@@ -367,6 +367,7 @@ struct Words16 {
     int32_t n;
 };
 hipError_t launch_store_words(unsigned long long* dst, const Words16& w, hipStream_t s);
+hipError_t launch_run_mark(const unsigned long long* out_count, unsigned long long* run_end, hipStream_t s);
 hipError_t launch_publish_words(const unsigned long long* src, int32_t n, unsigned long long* host,
                                 unsigned long long seq, hipStream_t s);
 hipError_t launch_widen_columns(const int32_t* k32, const uint32_t* t32, const int32_t* v32, int64_t n, int64_t tbase,

@@ -1244,6 +1244,21 @@ hipError_t launch_publish_words(const unsigned long long* src, int32_t n, unsign
     return hipGetLastError();
 }
 
+// run mode (fg_set_fired_runs): the fired-row count so far, stored where the host reads the end of
+// the run that closes here (coherent host memory) -- queued between two emitting launches of
+// different windows, so stream order makes it the boundary. One vector store by one lane.
+__global__ void k_run_mark(const unsigned long long* out_count, unsigned long long* run_end) {
+    if (threadIdx.x == 0) {
+        run_end[threadIdx.x] = *out_count;
+        __threadfence_system();
+    }
+}
+
+hipError_t launch_run_mark(const unsigned long long* out_count, unsigned long long* run_end, hipStream_t s) {
+    fg_launch(k_run_mark, dim3(1), dim3(64), 0, s, out_count, run_end);
+    return hipGetLastError();
+}
+
 hipError_t launch_pseudo_rowtime(const int64_t* slice_end, int64_t n, int64_t tz, int64_t* out, hipStream_t s) {
     int64_t blocks = (n + 255) / 256;
     blocks = blocks > 8192 ? 8192 : (blocks < 1 ? 1 : blocks);
@@ -1627,8 +1642,10 @@ template <bool NT = false>
 __device__ __forceinline__ void write_row_k(const MergeParams& p, unsigned long long o, int64_t key,
                                             unsigned long long cs, unsigned long long cn, const int64_t* vals, int vt) {
     ROW_ST(p.out_key[o], key);
-    ROW_ST(p.out_ws[o], p.wstart);
-    ROW_ST(p.out_we[o], p.wend);
+    // (run mode, fg_set_fired_runs: the per-fire constants are not stored -- null columns, a
+    // wave-uniform test on a kernel argument like the rowtime's)
+    if (p.out_ws) ROW_ST(p.out_ws[o], p.wstart);
+    if (p.out_we) ROW_ST(p.out_we[o], p.wend);
     if (p.out_rowtime) ROW_ST(p.out_rowtime[o], p.out_ts);
     const int64_t cv = (int64_t)(cs - cn);
     uint8_t nm = 0;

@@ -84,8 +84,10 @@ class WindowAggOperator:
                  buffer_records: int = 1 << 22, device: int = 0, max_parallelism: int = 128,
                  key_group_range=(0, 127), kernel_timing: bool = False, local_partials: bool = False,
                  proctime: bool = False, zone: str | None = None, windowed: bool = False,
-                 allowed_lateness: int = 0, purging_trigger: bool = False):
-        """allowed_lateness (DataStream): WindowedStream.allowedLateness -- a fired window keeps
+                 allowed_lateness: int = 0, purging_trigger: bool = False, fired_runs: bool = False):
+        """fired_runs: run mode (fg_set_fired_runs, see set_fired_runs).
+
+        allowed_lateness (DataStream): WindowedStream.allowedLateness -- a fired window keeps
         its state until maxTimestamp + allowed_lateness, and an element reaching it meanwhile
         fires it again at once; those rows are returned by the next process_watermark, ahead of
         the rows its watermark fires. purging_trigger: PurgingTrigger.of(EventTimeTrigger) (a
@@ -160,6 +162,13 @@ class WindowAggOperator:
         self._dev_rows = L.FgRows()   # process_watermark(device_output=True) result
         self._dev_rows_ref = C.byref(self._dev_rows)
         self._lib = lib
+        self._runs_on = False
+        if fired_runs:
+            try:
+                self.set_fired_runs(True)
+            except Exception:
+                self.close()
+                raise
 
     # -- lifecycle -------------------------------------------------------------------------
     def close(self):
@@ -382,6 +391,33 @@ class WindowAggOperator:
         L.check(self._lib.fg_collect_fired(self._h, self._dev_rows_ref), self._h)
         return self._dev_rows
 
+    # -- fired rows as runs ---------------------------------------------------------------------
+    def set_fired_runs(self, on: bool = True):
+        """fg_set_fired_runs: in run mode the fired rows carry no window_start, window_end and
+        rowtime columns (not stored by the kernels, not allocated, not copied to the host; device
+        FgRows hold NULL pointers for them) and fired_runs() says which row range belongs to
+        which window. The structured arrays this operator returns are the same as without it: the
+        three columns are expanded from the runs on the host. Refused (WindowSpecError) for a
+        local_partials operator and with allowed_lateness > 0, and (FlinkGpuError, FG_ESTATE)
+        while fired rows are not collected."""
+        L.check(self._lib.fg_set_fired_runs(self._h, 1 if on else 0), self._h)
+        self._runs_on = bool(on)
+
+    def fired_runs(self) -> dict:
+        """fg_fired_runs: the runs of the rows the last process_watermark / collect_fired returned
+        -- int64 numpy columns window_start, window_end, rowtime (= window_end - 1), first_row,
+        rows; run i covers rows [first_row[i], first_row[i] + rows[i]). A window may appear in more
+        than one run (the rows of a state region redone after it overflowed come last)."""
+        rr = L.FgRowRuns()
+        L.check(self._lib.fg_fired_runs(self._h, C.byref(rr)), self._h)
+        n = int(rr.n)
+
+        def col(p):
+            if n == 0:
+                return np.zeros(0, dtype=np.int64)
+            return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_int64)), shape=(n,)).copy()
+        return {k: col(getattr(rr, k)) for k in RUN_COLUMNS}
+
     def rows_to_host(self, r: L.FgRows) -> np.ndarray:
         """Host copy of device FgRows (process_watermark(device_output=True) / collect_fired) in the
         layout of the host rows."""
@@ -418,8 +454,12 @@ class WindowAggOperator:
                 return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(dtype)), shape=(count,)).copy()
 
         out["key"] = col(r.key, C.c_int64, n)
-        out["window_start"] = col(r.window_start, C.c_int64, n)
-        out["window_end"] = col(r.window_end, C.c_int64, n)
+        if self._runs_on:   # run mode: the window columns of r are NULL, the runs hold them
+            ws, we, rt = expand_runs(self.fired_runs(), n)
+            out["window_start"], out["window_end"] = ws, we
+        else:
+            out["window_start"] = col(r.window_start, C.c_int64, n)
+            out["window_end"] = col(r.window_end, C.c_int64, n)
         nullm = col(r.null_mask, C.c_uint8, n)
         for i, a in enumerate(self.aggs):
             nm = AGG_NAMES[a]
@@ -427,7 +467,7 @@ class WindowAggOperator:
             out[nm] = raw.view(np.float64) if out.dtype[nm] == np.float64 else raw
             out[nm + "_null"] = (nullm >> i) & 1 == 1
         if self.mode == L.MODE_DATASTREAM:
-            out["rowtime"] = col(r.rowtime, C.c_int64, n)
+            out["rowtime"] = rt if self._runs_on else col(r.rowtime, C.c_int64, n)
         return out
 
     # -- checkpointing ----------------------------------------------------------------------------
@@ -656,6 +696,31 @@ class WindowAggOperator:
     @property
     def stream(self) -> int:
         return self._lib.fg_stream(self._h) or 0
+
+
+RUN_COLUMNS = ("window_start", "window_end", "rowtime", "first_row", "rows")
+
+
+def expand_runs(runs: dict, n: int):
+    """(window_start, window_end, rowtime) columns of `n` fired rows from their run directory
+    (WindowAggOperator.fired_runs): each run's window repeated over its rows. ValueError for a
+    directory that is not one: runs that do not start at row 0, leave a gap or overlap, a run
+    without rows, rows that do not sum to n, a rowtime that is not window_end - 1."""
+    cols = [np.asarray(runs[k], dtype=np.int64) for k in RUN_COLUMNS]
+    ws, we, rt, first, rows = cols
+    if any(c.ndim != 1 or len(c) != len(we) for c in cols):
+        raise ValueError("fired runs: the columns differ in length")
+    if len(rows) and rows.min() <= 0:
+        raise ValueError("fired runs: a run without rows")
+    ends = np.cumsum(rows)
+    if len(rows) and (first[0] != 0 or not np.array_equal(first[1:], ends[:-1])):
+        raise ValueError("fired runs: first_row is not the running sum of rows (a gap or an overlap)")
+    if (int(ends[-1]) if len(rows) else 0) != int(n):
+        raise ValueError(f"fired runs: the runs hold {int(ends[-1]) if len(rows) else 0} rows, not {int(n)}")
+    with np.errstate(over="ignore"):
+        if not np.array_equal(rt, we - np.int64(1)):   # (Java subtraction: wraps)
+            raise ValueError("fired runs: rowtime is not window_end - 1")
+    return np.repeat(ws, rows), np.repeat(we, rows), np.repeat(rt, rows)
 
 
 def key_groups(keys, max_parallelism: int = 128, key_hash: int = L.KEYHASH_BINARYROW_BIGINT, device: int = 0):

@@ -207,11 +207,11 @@ typedef struct fg_rows {
     int32_t location;             /* where the column pointers live */
     int32_t num_aggs;
     const int64_t* key;
-    const int64_t* window_start;
+    const int64_t* window_start;       /* window_start, window_end: NULL in run mode (fg_set_fired_runs) */
     const int64_t* window_end;
     const int64_t* agg[FG_MAX_AGGS];   /* 8-byte columns: BIGINT, or the bits of a DOUBLE */
     const uint8_t* null_mask;          /* bit i set: agg[i] is NULL in that row */
-    const int64_t* rowtime;            /* DataStream: window.maxTimestamp() (end - 1); SQL: NULL */
+    const int64_t* rowtime;            /* DataStream: window.maxTimestamp() (end - 1); SQL, run mode: NULL */
 } fg_rows;
 
 /* Packed BinaryRowData input: the records as Flink holds them (BinaryRowData.java:68-76): row i
@@ -401,6 +401,43 @@ typedef struct fg_image_key_groups {
                                   * rows [first_row[s*maxp+g], first_row[s*maxp+g+1]) */
 } fg_image_key_groups;
 int  fg_snapshot_key_groups(fg_handle* h, fg_image_key_groups* out);
+/* Fired rows as runs (ABI 16, added): every row of one fire carries the same window_start, window_end
+ * and (DataStream) rowtime = end - 1. A handle in run mode returns its fired rows without these
+ * columns and says once per run which window a range of rows belongs to.
+ * fg_set_fired_runs(h, on != 0) turns run mode on, 0 turns it off (the default). Idempotent.
+ *  - FG_EINVAL (turning on): a FG_FLAG_LOCAL_PARTIALS handle -- its rows feed fg_comm_* and
+ *    fg_partition_*, which read window_end per row; a handle with allowed_lateness_ms > 0 -- late
+ *    elements fire rows whose window differs per row.
+ *  - FG_ESTATE: fired rows are not collected yet, or a fire is pending (after
+ *    fg_advance_progress_async: fg_collect_fired first).
+ *    fg_last_error names the reason. The handle stays usable after an error.
+ * In run mode every call that returns fg_rows -- fg_advance_progress, fg_collect_fired,
+ * fg_collect_fired_to -- fills key, agg[], null_mask, n and num_aggs as always and leaves
+ * window_start, window_end and rowtime NULL, for FG_DEVICE and FG_HOST alike. The handle holds no
+ * device or host memory for the three columns (16 of 8 x (3 + aggs) + 1 bytes per SQL row, 24 per
+ * DataStream row), the kernels do not store them and no copy moves them.
+ * fg_fired_runs: the runs of the rows the last such call returned, in library-owned host memory,
+ * valid until the next call that fires windows (or fg_reset, fg_restore, fg_set_fired_runs); n = 0
+ * when that call returned no rows. FG_ESTATE when run mode is off. Run i covers rows
+ * [first_row[i], first_row[i] + rows[i]):
+ *  - first_row[0] = 0, first_row[i + 1] = first_row[i] + rows[i], every rows[i] > 0, and the rows sum
+ *    to fg_rows.n;
+ *  - rowtime[i] = window_end[i] - 1 (Java subtraction; also filled for a SQL handle);
+ *  - adjacent runs never share a window_end, but a window may appear in more than one run: the rows
+ *    a state region re-emits after it overflowed and was split follow the rows of the windows fired
+ *    after it. A consumer must not assume one run per window;
+ *  - rows of fg_advance_progress_async calls not yet collected that lead a synchronous advance's
+ *    rows keep their runs, in order. */
+typedef struct fg_row_runs {
+    int64_t n;
+    const int64_t* window_start;   /* [n] */
+    const int64_t* window_end;     /* [n] */
+    const int64_t* rowtime;        /* [n] window_end - 1 */
+    const int64_t* first_row;      /* [n] */
+    const int64_t* rows;           /* [n] */
+} fg_row_runs;
+int  fg_set_fired_runs(fg_handle* h, int32_t on);
+int  fg_fired_runs(fg_handle* h, fg_row_runs* out);
 /* Selective images (ABI 16, added): a checkpoint that exports and copies only the slices its caller
  * needs. The engine says what is resident and what changed (plan), the caller answers with a mask
  * (a shim's policy needs more than the changed slices: a CUMULATE namespace is rebuilt from all its

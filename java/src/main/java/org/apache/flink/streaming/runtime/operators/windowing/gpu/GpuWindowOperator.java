@@ -188,6 +188,8 @@ public final class GpuWindowOperator<V, ACC, OUT> extends AbstractStreamOperator
     private final boolean purging;
 
     private transient long handle;
+    /** the handle is in run mode (FgConfig.firedRuns): fired rows carry no window columns */
+    private transient boolean firedRuns;
     private transient ByteBuffer keys, timestamps, vals;
     private transient int count;
     private transient long droppedSeen;
@@ -289,6 +291,10 @@ public final class GpuWindowOperator<V, ACC, OUT> extends AbstractStreamOperator
                                 0),
                         null,
                         null);
+        firedRuns = FgConfig.firedRuns && spec.allowedLatenessMs == 0;   // (lateness: a window per row)
+        if (firedRuns) {
+            FlinkGpu.setFiredRuns(handle, true);
+        }
         keys = direct(8L * spec.batchRecords);
         timestamps = direct(8L * spec.batchRecords);
         vals = hasValue ? direct(8L * spec.batchRecords) : null;
@@ -350,9 +356,21 @@ public final class GpuWindowOperator<V, ACC, OUT> extends AbstractStreamOperator
             }
         }
         // columns: key, window_start, window_end, COUNT(*)[, the value aggregate], null mask, rowtime
+        // (run mode: no window_start, window_end, rowtime; the window end of row i is its run's,
+        // runs = [n, start[n], end[n], firstRow[n], rows[n]])
+        long[] runs = firedRuns ? FlinkGpu.firedRuns(handle) : null;
+        int nRuns = runs == null ? 0 : (int) runs[0];
+        int run = -1;
+        long runLast = -1;   // last row of the current run
+        long runEnd = 0;
         for (int i = 0; i < n; i++) {
+            if (runs != null && i > runLast) {
+                run++;
+                runLast = runs[1 + 2 * nRuns + run] + runs[1 + 3 * nRuns + run] - 1;
+                runEnd = runs[1 + nRuns + run];
+            }
             long key = cols[0].getLong(8 * i);
-            long end = cols[2].getLong(8 * i);
+            long end = runs != null ? runEnd : cols[2].getLong(8 * i);
             long a1 = cols[3].getLong(8 * i);
             long a0 = hasValue ? cols[4].getLong(8 * i) : 0L;
             Restored r = restored.get(end);

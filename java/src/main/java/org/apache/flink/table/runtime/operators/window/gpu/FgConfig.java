@@ -56,6 +56,13 @@ public final class FgConfig {
     public static final int FLAG_WINDOWED = 8;
     public static final int FLAG_PURGING_TRIGGER = 16;
 
+    /**
+     * Run mode (fg_set_fired_runs) for the handles the shim opens that qualify -- no local phase, no
+     * allowed lateness: fired rows come without their window columns, the row builders take the
+     * window from FlinkGpu.firedRuns. Off by default (-Dflinkgpu.firedRuns=true turns it on).
+     */
+    public static boolean firedRuns = Boolean.getBoolean("flinkgpu.firedRuns");
+
     private FgConfig() {}
 
     /** The image of spec for the subtask owning key groups [kgStart, kgEnd]. */

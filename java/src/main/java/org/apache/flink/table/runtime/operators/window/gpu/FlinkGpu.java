@@ -67,7 +67,8 @@ public final class FlinkGpu {
 
     /**
      * fg_advance_progress: fills cols with key, window_start, window_end, agg[0..numAggs),
-     * null_mask, rowtime (library-owned, valid until the next call); returns the row count.
+     * null_mask, rowtime (library-owned, valid until the next call); returns the row count. In run
+     * mode ({@link #setFiredRuns}) the window_start, window_end and rowtime entries stay null.
      */
     public static native long advanceProgress(long h, long watermark, ByteBuffer[] cols);
 
@@ -85,6 +86,23 @@ public final class FlinkGpu {
      * collect; fills cols as {@link #advanceProgress} (host memory); returns the row count.
      */
     public static native long collectFired(long h, ByteBuffer[] cols);
+
+    /**
+     * fg_set_fired_runs (ABI 16): run mode -- advanceProgress and collectFired leave the
+     * window_start, window_end and rowtime entries of cols null (the engine neither stores nor
+     * copies these per-fire constants) and {@link #firedRuns} says which rows belong to which
+     * window. Refused for FG_FLAG_LOCAL_PARTIALS handles and with allowed lateness
+     * (IllegalArgumentException), and while fired rows are uncollected.
+     */
+    public static native void setFiredRuns(long h, boolean on);
+
+    /**
+     * fg_fired_runs: the runs of the rows the last advanceProgress / collectFired returned, as
+     * [n, windowStart[n], windowEnd[n], firstRow[n], rows[n]]: run i covers rows [firstRow[i],
+     * firstRow[i] + rows[i]); their rowtime is windowEnd[i] - 1. A window may appear in more than
+     * one run.
+     */
+    public static native long[] firedRuns(long h);
 
     /** fg_flush (prepareSnapshotPreBarrier). */
     public static native void flush(long h);

@@ -93,6 +93,8 @@ public final class GpuSlicingWindowProcessor implements SlicingWindowProcessor<L
     /** an fg_snapshot_state_async not collected (a checkpoint that failed before its wait). */
     private transient boolean snapshotPending;
     private transient boolean batchHanded;
+    /** the handle is in run mode (FgConfig.firedRuns): fired rows carry no window columns */
+    private transient boolean firedRuns;
     /** the namespaces the backend holds from the last image written (or restored), and their slices */
     private transient Map<Long, Set<Long>> imageContrib;
     /** the next window end the key timers of fired state were registered at */
@@ -125,6 +127,10 @@ public final class GpuSlicingWindowProcessor implements SlicingWindowProcessor<L
                         FgConfig.of(spec, maxP, range.getStartKeyGroup(), range.getEndKeyGroup(), nTz),
                         spec.tzTransitionsMs,
                         spec.tzOffsetsMs);
+        firedRuns = FgConfig.firedRuns && (spec.flags & FgConfig.FLAG_LOCAL_PARTIALS) == 0;
+        if (firedRuns) {
+            FlinkGpu.setFiredRuns(handle, true);
+        }
         keys = new GpuKeyRows(spec, maxP);
         accRows = new GpuAccRows(spec.aggs, spec.valType);
         int b = spec.batchRecords;
@@ -299,7 +305,19 @@ public final class GpuSlicingWindowProcessor implements SlicingWindowProcessor<L
         }
         int nAggs = spec.aggs.length;
         RowData[] keyRows = keys.rows(cols[0], (int) n);
+        // run mode: cols[1] and cols[2] are null; run r = [n, start[n], end[n], firstRow[n], rows[n]]
+        long[] runs = firedRuns ? FlinkGpu.firedRuns(handle) : null;
+        int nRuns = runs == null ? 0 : (int) runs[0];
+        int run = -1;
+        long runLast = -1;   // last row of the current run
+        TimestampData runStart = null, runEnd = null;
         for (int i = 0; i < n; i++) {
+            if (runs != null && i > runLast) {
+                run++;
+                runLast = runs[1 + 2 * nRuns + run] + runs[1 + 3 * nRuns + run] - 1;
+                runStart = TimestampData.fromEpochMillis(runs[1 + run]);
+                runEnd = TimestampData.fromEpochMillis(runs[1 + nRuns + run]);
+            }
             byte nullMask = cols[3 + nAggs].get(i);
             GenericRowData aggs = new GenericRowData(nAggs + 2);
             for (int a = 0; a < nAggs; a++) {
@@ -315,8 +333,8 @@ public final class GpuSlicingWindowProcessor implements SlicingWindowProcessor<L
                                 ? (Object) Double.longBitsToDouble(bits)
                                 : (Object) bits);
             }
-            aggs.setField(nAggs, TimestampData.fromEpochMillis(cols[1].getLong(8 * i)));
-            aggs.setField(nAggs + 1, TimestampData.fromEpochMillis(cols[2].getLong(8 * i)));
+            aggs.setField(nAggs, runs != null ? runStart : TimestampData.fromEpochMillis(cols[1].getLong(8 * i)));
+            aggs.setField(nAggs + 1, runs != null ? runEnd : TimestampData.fromEpochMillis(cols[2].getLong(8 * i)));
             ctx.output(new JoinedRowData(keyRows[i], aggs));
         }
         long dropped = FlinkGpu.lateDropped(handle);

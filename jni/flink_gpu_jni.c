@@ -193,7 +193,9 @@ JNIEXPORT void JNICALL FN(addPartials)(JNIEnv* env, jclass cls, jlong hp, jint n
 }
 
 /* the columns of fg_rows into cols (length >= 5 + num_aggs): key, window_start, window_end,
- * agg[0..num_aggs), null_mask, rowtime (DataStream; else null); returns the row count */
+ * agg[0..num_aggs), null_mask, rowtime (DataStream; else null); returns the row count. In run mode
+ * (setFiredRuns) window_start, window_end and rowtime are absent: their entries are null, and
+ * firedRuns says which rows belong to which window. */
 static jlong put_rows(JNIEnv* env, const fg_rows* r, jobjectArray cols, const char* who) {
     const jlong n = r->n, bytes = 8 * n;
     if ((*env)->GetArrayLength(env, cols) < 5 + r->num_aggs) {
@@ -204,8 +206,8 @@ static jlong put_rows(JNIEnv* env, const fg_rows* r, jobjectArray cols, const ch
     }
     int i = 0;
     (*env)->SetObjectArrayElement(env, cols, i++, wrap(env, r->key, bytes));
-    (*env)->SetObjectArrayElement(env, cols, i++, wrap(env, r->window_start, bytes));
-    (*env)->SetObjectArrayElement(env, cols, i++, wrap(env, r->window_end, bytes));
+    (*env)->SetObjectArrayElement(env, cols, i++, r->window_start ? wrap(env, r->window_start, bytes) : NULL);
+    (*env)->SetObjectArrayElement(env, cols, i++, r->window_end ? wrap(env, r->window_end, bytes) : NULL);
     for (int a = 0; a < r->num_aggs; a++) (*env)->SetObjectArrayElement(env, cols, i++, wrap(env, r->agg[a], bytes));
     (*env)->SetObjectArrayElement(env, cols, i++, wrap(env, r->null_mask, n));
     (*env)->SetObjectArrayElement(env, cols, i++, r->rowtime ? wrap(env, r->rowtime, bytes) : NULL);
@@ -254,6 +256,37 @@ JNIEXPORT jlong JNICALL FN(collectFired)(JNIEnv* env, jclass cls, jlong hp, jobj
     fg_rows r;
     if (check(env, h, fg_collect_fired_to(h, FG_HOST, &r))) return 0;
     return put_rows(env, &r, cols, "collectFired");
+}
+
+/* void setFiredRuns(long h, boolean on): run mode (fg_set_fired_runs, ABI 16) -- the fired rows come
+ * without their window_start, window_end and rowtime columns */
+JNIEXPORT void JNICALL FN(setFiredRuns)(JNIEnv* env, jclass cls, jlong hp, jboolean on) {
+    (void)cls;
+    fg_handle* h = (fg_handle*)(intptr_t)hp;
+    (void)check(env, h, fg_set_fired_runs(h, on ? 1 : 0));
+}
+
+/* long[] firedRuns(long h): the runs of the rows the last advanceProgress / collectFired returned
+ * (fg_fired_runs) as one array: [n, window_start[n], window_end[n], first_row[n], rows[n]] -- run i
+ * covers rows [first_row[i], first_row[i] + rows[i]); its rowtime is window_end[i] - 1. A window may
+ * appear in more than one run. */
+JNIEXPORT jlongArray JNICALL FN(firedRuns)(JNIEnv* env, jclass cls, jlong hp) {
+    (void)cls;
+    fg_handle* h = (fg_handle*)(intptr_t)hp;
+    fg_row_runs r;
+    if (check(env, h, fg_fired_runs(h, &r))) return NULL;
+    const jsize n = (jsize)r.n;
+    jlongArray out = (*env)->NewLongArray(env, 1 + 4 * n);
+    if (!out) return NULL;
+    const jlong head = n;
+    (*env)->SetLongArrayRegion(env, out, 0, 1, &head);
+    if (n > 0) {
+        (*env)->SetLongArrayRegion(env, out, 1, n, (const jlong*)r.window_start);
+        (*env)->SetLongArrayRegion(env, out, 1 + n, n, (const jlong*)r.window_end);
+        (*env)->SetLongArrayRegion(env, out, 1 + 2 * n, n, (const jlong*)r.first_row);
+        (*env)->SetLongArrayRegion(env, out, 1 + 3 * n, n, (const jlong*)r.rows);
+    }
+    return out;
 }
 
 /* void flush(long h) */

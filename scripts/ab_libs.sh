@@ -1,10 +1,11 @@
 # A/B of variant libraries on one box: the headline bench (or --workload W) per library, in
 # rotation, printing ms/step and the dominant kernels' average launch times.
-# Usage: bash scripts/ab_libs.sh TAG "bench args" lib1 lib2 ...   (lib: a dir under flink_amd/variants)
+# Usage: [REPS=3] bash scripts/ab_libs.sh TAG "bench args" lib1 lib2 ...   (lib: a dir under flink_amd/variants)
+# REPS: rotations, i.e. runs per library (default 2)
 set -o pipefail
 O=gpurun_out/$1; ARGS=$2; shift 2
 mkdir -p $O
-for rep in 1 2; do
+for rep in $(seq ${REPS:-2}); do
   for v in "$@"; do
     FLINKGPU_LIB=$PWD/flink_amd/variants/$v/libflinkgpu.so timeout -k 10 240 python bench.py --no-cpu-baseline --h2d-records 0 $ARGS \
       > $O/${v}_$rep.log 2>&1 || { echo "bench $v failed"; tail -5 $O/${v}_$rep.log; exit 1; }
