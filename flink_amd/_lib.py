@@ -104,6 +104,11 @@ class FgRowRuns(C.Structure):
                 ("first_row", C.c_void_p), ("rows", C.c_void_p)]
 
 
+class FgLateRecords(C.Structure):
+    _fields_ = [("n", C.c_int64), ("location", C.c_int32), ("reserved0", C.c_int32), ("key", C.c_void_p),
+                ("rowtime", C.c_void_p), ("val", C.c_void_p), ("val_null", C.c_void_p)]
+
+
 class FgStats(C.Structure):
     _fields_ = [(n, C.c_int64) for n in (
         "records_in", "records_staged", "late_dropped", "rows_fired", "flushes", "live_slices",
@@ -135,6 +140,7 @@ EXPORTS = (
     "fg_set_snapshot_grouping", "fg_snapshot_key_groups",
     "fg_snapshot_plan", "fg_snapshot_state_select_async", "fg_snapshot_state_select",
     "fg_set_fired_runs", "fg_fired_runs",
+    "fg_set_late_output", "fg_collect_late",
     "fg_stream",
     "fg_last_error", "fg_close", "fg_key_groups", "fg_partition_by_owner", "fg_partition_columns_by_owner",
     "fg_abi_version", "fg_key_dict_open", "fg_key_dict_intern", "fg_key_dict_intern_async",
@@ -269,6 +275,10 @@ def load():
         L.fg_set_fired_runs.argtypes = [P, C.c_int32]
         L.fg_fired_runs.argtypes = [P, C.POINTER(FgRowRuns)]
         L.fg_set_fired_runs.restype = L.fg_fired_runs.restype = C.c_int
+    if hasattr(L, "fg_set_late_output"):   # (the same: asking an older variant library for it raises)
+        L.fg_set_late_output.argtypes = [P, C.c_int32]
+        L.fg_collect_late.argtypes = [P, C.c_int32, C.POINTER(FgLateRecords)]
+        L.fg_set_late_output.restype = L.fg_collect_late.restype = C.c_int
     L.fg_selftest.argtypes = [C.c_int32, C.c_char_p, C.c_int32]
     L.fg_selftest.restype = C.c_int
     L.fg_comm_bytes_sent.argtypes = [P]

@@ -175,12 +175,13 @@ constexpr int64_t kHeavyChunk = 1 << 16;
 
 enum KClass { K_COUNT = 0, K_SCAN, K_SCATTER, K_PART1, K_PART2, K_FLUSH, K_FLUSH_FIRE, K_FIRE, K_EXPORT, K_RESTORE,
               K_HEAVY, K_TILE1, K_TILE_FIRE, K_TILE_MAT, K_TILE_FLUSH, K_TILE_SPLIT, K_RR_FILTER, K_RR_SCATTER,
-              K_EXPORT_GROUP, K_EXPORT_SELECT, K_NCLASS };
+              K_EXPORT_GROUP, K_EXPORT_SELECT, K_LATE_OUT, K_NCLASS };
 const char* const kClassName[K_NCLASS] = {"ingest_count", "ingest_scan",      "ingest_scatter", "ingest_part1",
                                            "ingest_part2", "merge_flush",      "merge_flush_fire", "merge_fire",
                                            "export",       "restore",          "merge_heavy",      "tile_part1",
                                            "tile_fire",    "tile_materialize", "tile_flush",       "tile_split_fire",
-                                           "restore_filter", "restore_scatter", "export_group",   "export_select"};
+                                           "restore_filter", "restore_scatter", "export_group",   "export_select",
+                                           "late_out"};
 struct KStat {
     int64_t launches = 0;
     double ms = 0;
@@ -490,6 +491,16 @@ struct fg_handle {
     DevBuf lt_mix, lt_se, lt_val, lt_null, lt_idx, lt_done, lt_sel, lt_slot, lt_found, lt_ckey, lt_cidx, lt_need;
     DevBuf lt_dir_se, lt_dir_t, lt_words, lt_r_key, lt_r_ts, lt_r_val, lt_r_null;
     HostBuf lt_h;
+    // Late-element side output (fg_set_late_output, fg_late_out.hip): the elements the ingest drops,
+    // kept in arrival order in lo_key / lo_ts / lo_val / lo_null until fg_collect_late. lo_words:
+    // {records not yet collected, records that found no room} on the device; lo_known: the same
+    // total as the host knows it from the settled batches' drop counts.
+    bool late_out = false;
+    bool lo_listed = false;     // the mode was on at some time: fg_kernel_stats lists the class late_out
+    bool lo_has_null = false;   // some batch since the last collect carried val_null
+    int64_t lo_known = 0;
+    DevBuf lo_key, lo_ts, lo_val, lo_null, lo_words, lo_cnt, lo_base;
+    HostBuf lo_h_key, lo_h_ts, lo_h_val, lo_h_null, lo_h_words;
 
     // stats
     int64_t records_in = 0, rows_fired = 0, flushes = 0;
@@ -3151,7 +3162,12 @@ int finish_batch(fg_handle* h) {
     Counters c{};
     int rc = ingest_finish(h, pb.ps, &c);
     pb.ps = PassState{};
-    h->late_dropped += (int64_t)c.drops;
+    if (h->late_out) {   // side-output instead (the reference counts only in the else branch)
+        h->lo_known += (int64_t)c.drops;
+        h->kstat[K_LATE_OUT].rows += (int64_t)c.drops;
+    } else {
+        h->late_dropped += (int64_t)c.drops;
+    }
     if (rc != FG_OK && rc != -1) return rc;
     if (c.qmin > c.qmax) return FG_OK;   // nothing accepted
     h->q_guess = (uint64_t)(c.qmax - c.qmin) >= (uint64_t)h->lanes ? c.qmin : kEmptyLane;
@@ -3382,6 +3398,58 @@ int late_split(fg_handle* h, int64_t n, const int64_t** key, const int64_t** ts,
     *ts = h->lt_r_ts.as<int64_t>();
     if (*val) *val = h->lt_r_val.as<int64_t>();
     if (*vnull) *vnull = h->lt_r_null.as<uint8_t>();
+    return FG_OK;
+}
+
+// Late-element side output: the batch's elements the ingest is about to drop (ds_dropped) are
+// appended to the late-record columns, on the handle's stream ahead of late_split / the ingest.
+// The columns hold every record the host knows of plus, as a worst case, all of an unsettled
+// batch and of this one; growing them copies their content in stream order (DevBuf::ensure with
+// keep: behind every queued scatter, and waited for before the old columns are freed).
+int late_out_pass(fg_handle* h, int64_t n, const int64_t* key, const int64_t* ts, const int64_t* val,
+                  const uint8_t* vnull) {
+    const int64_t need = h->lo_known + (h->pending.active ? h->pending.n : 0) + n;
+    const int64_t cap = (int64_t)(h->lo_key.bytes / 8);
+    if (need > cap) {
+        const size_t want = (size_t)std::max<int64_t>(need, 2 * cap);
+        HIPCHK(h, h->lo_key.ensure(8 * want, h->stream, true));
+        HIPCHK(h, h->lo_ts.ensure(8 * want, h->stream, true));
+        if (h->cfg.val_type != FG_VAL_NONE) HIPCHK(h, h->lo_val.ensure(8 * want, h->stream, true));
+        HIPCHK(h, h->lo_null.ensure(want, h->stream, true));
+    }
+    LateOut p{};
+    p.w = h->w;
+    p.progress = h->current_progress;   // (IngestParams.progress of a DataStream handle)
+    p.late_wm = late_wm(h);
+    p.lateness = h->lateness;
+    p.purging = h->purging ? 1 : 0;
+    p.n = n;
+    p.n_chunks = (int32_t)((n + kLateOutChunk - 1) / kLateOutChunk);
+    HIPCHK(h, h->lo_cnt.ensure(4 * (size_t)p.n_chunks));
+    HIPCHK(h, h->lo_base.ensure(8 * (size_t)p.n_chunks));
+    p.key = key;
+    p.ts = ts;
+    p.val = h->cfg.val_type != FG_VAL_NONE ? val : nullptr;
+    p.vnull = vnull;
+    p.chunk_cnt = h->lo_cnt.as<uint32_t>();
+    p.chunk_base = h->lo_base.as<unsigned long long>();
+    p.total = h->lo_words.as<unsigned long long>();
+    p.cap = (int64_t)std::min(h->lo_key.bytes / 8, h->lo_null.bytes);
+    p.o_key = h->lo_key.as<int64_t>();
+    p.o_ts = h->lo_ts.as<int64_t>();
+    p.o_val = p.val ? h->lo_val.as<int64_t>() : nullptr;
+    p.o_null = h->lo_null.as<uint8_t>();
+    if (vnull) h->lo_has_null = true;
+    KTimer kt(h, K_LATE_OUT, n);
+    HIPCHK(h, launch_late_out(p, h->stream));
+    return FG_OK;
+}
+
+// uncollected late records are not operator state: fg_reset and the restores discard them
+int late_out_discard(fg_handle* h) {
+    h->lo_known = 0;
+    h->lo_has_null = false;
+    if (h->late_out) HIPCHK(h, hipMemsetAsync(h->lo_words.p, 0, 16, h->stream));
     return FG_OK;
 }
 
@@ -3877,6 +3945,9 @@ int fg_add_batch(fg_handle* h, const fg_batch* b) {
             return h->fail(FG_EINVAL, "windowed input: %llu window_end values off the slice grid of the window", nbad);
         ts = h->in_wts.as<int64_t>();
     }
+    // side output of late elements: copied out ahead of the ingest, which goes on discarding them
+    if (h->late_out)
+        if (int rco = late_out_pass(h, n, key, ts, val, vnull)) return rco;
     // DataStream allowed lateness: elements of fired, not yet cleaned windows FIRE them now
     // (late_split / late_fire); the rest go on as the batch
     if (h->lateness > 0) {
@@ -4676,6 +4747,83 @@ int fg_fired_runs(fg_handle* h, fg_row_runs* out) {
     return FG_OK;
 }
 
+int fg_set_late_output(fg_handle* h, int32_t on) {
+    if (!h) return FG_EINVAL;
+    h->snap.plan_valid = false;
+    const bool want = on != 0;
+    if (want && (h->cfg.mode != FG_MODE_DATASTREAM || h->local || h->proctime || h->windowed))
+        return h->fail(FG_EINVAL, "fg_set_late_output: sideOutputLateData is a DataStream WindowOperator setting (SQL "
+                                  "window operators have no side output)");
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc0 = settle_pending(h)) return rc0;   // (a batch taken under the old mode counts under it)
+    if (want == h->late_out) return FG_OK;
+    if (!want && h->lo_known > 0)
+        return h->fail(FG_ESTATE, "fg_set_late_output: %lld late records are not collected yet (fg_collect_late first)",
+                       (long long)h->lo_known);
+    if (want) {
+        HIPCHK(h, h->lo_words.ensure(16));
+        HIPCHK(h, h->lo_h_words.ensure(16));
+        HIPCHK(h, hipMemsetAsync(h->lo_words.p, 0, 16, h->stream));
+    }
+    h->late_out = want;
+    if (want) h->lo_listed = true;
+    return FG_OK;
+}
+
+int fg_collect_late(fg_handle* h, int32_t out_location, fg_late_records* out) {
+    if (!h || !out) return FG_EINVAL;
+    h->snap.plan_valid = false;
+    if (out_location != FG_HOST && out_location != FG_DEVICE)
+        return h->fail(FG_EINVAL, "fg_collect_late: unknown location %d", out_location);
+    if (!h->late_out) return h->fail(FG_ESTATE, "fg_collect_late: the late output is off (fg_set_late_output)");
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc0 = settle_pending(h)) return rc0;
+    std::memset(out, 0, sizeof *out);
+    out->location = out_location;
+    // the device's total against the drop counts of the settled batches: the compaction and the
+    // ingest took the same decision for every element, or the answer is refused
+    HIPCHK(h, hipMemcpyAsync(h->lo_h_words.p, h->lo_words.p, 16, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemsetAsync(h->lo_words.p, 0, 16, h->stream));
+    if (int rc = sync(h)) return rc;
+    const unsigned long long dev_n = h->lo_h_words.as<unsigned long long>()[0];
+    const unsigned long long dev_lost = h->lo_h_words.as<unsigned long long>()[1];
+    const int64_t n = h->lo_known;
+    const bool has_null = h->lo_has_null;
+    h->lo_known = 0;   // drained, also when refused
+    h->lo_has_null = false;
+    if (dev_n != (unsigned long long)n || dev_lost != 0)
+        return h->fail(FG_ESTATE, "internal: late output and ingest disagree (%llu records kept, %llu without room, "
+                                  "%lld dropped by the ingest)", dev_n, dev_lost, (long long)n);
+    out->n = n;
+    if (n == 0) return FG_OK;
+    const bool has_val = h->cfg.val_type != FG_VAL_NONE;
+    if (out_location == FG_DEVICE) {
+        out->key = h->lo_key.as<int64_t>();
+        out->rowtime = h->lo_ts.as<int64_t>();
+        out->val = has_val ? h->lo_val.p : nullptr;
+        out->val_null = has_null ? h->lo_null.as<uint8_t>() : nullptr;
+        return FG_OK;
+    }
+    HIPCHK(h, h->lo_h_key.ensure(8 * (size_t)n));
+    HIPCHK(h, h->lo_h_ts.ensure(8 * (size_t)n));
+    HIPCHK(h, hipMemcpyAsync(h->lo_h_key.p, h->lo_key.p, 8 * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->lo_h_ts.p, h->lo_ts.p, 8 * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    if (has_val) {
+        HIPCHK(h, h->lo_h_val.ensure(8 * (size_t)n));
+        HIPCHK(h, hipMemcpyAsync(h->lo_h_val.p, h->lo_val.p, 8 * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    }
+    if (has_null) {
+        HIPCHK(h, h->lo_h_null.ensure((size_t)n));
+        HIPCHK(h, hipMemcpyAsync(h->lo_h_null.p, h->lo_null.p, (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    }
+    if (int rc = sync(h)) return rc;
+    out->key = h->lo_h_key.as<int64_t>();
+    out->rowtime = h->lo_h_ts.as<int64_t>();
+    out->val = has_val ? h->lo_h_val.p : nullptr;
+    out->val_null = has_null ? h->lo_h_null.as<uint8_t>() : nullptr;
+    return FG_OK;
+}
+
 int fg_snapshot_key_groups(fg_handle* h, fg_image_key_groups* out) {
     if (!h || !out) return FG_EINVAL;
     h->snap.plan_valid = false;
@@ -4810,7 +4958,7 @@ static int restore_finish(fg_handle* h, int64_t timer_watermark, bool was_empty)
     // write reaches it (the shim's next checkpoint rewrites only the slices that change)
     if (was_empty)
         for (auto& kv : h->tables) kv.second->changed = false;
-    return FG_OK;
+    return late_out_discard(h);
 }
 
 // One K_RESTORE merge: the `m` rows of a restore batch that belong to the slice ending at
@@ -5135,6 +5283,7 @@ int fg_reset(fg_handle* h) {
     h->retire_at.clear();
     h->late_rows = 0;
     h->late_horizon = JMIN;
+    if (int rcl = late_out_discard(h)) return rcl;
     h->narrow = h->narrow_ok;
     h->tile_ok = true;
     return FG_OK;
@@ -5145,8 +5294,12 @@ int fg_kernel_stats(fg_handle* h, fg_kernel_stat* out, int32_t max, int32_t* cou
     if (int rc0 = settle_pending(h)) return rc0;
     int rc = sync(h, true);
     if (rc) return rc;
-    *count = K_NCLASS;
-    for (int c = 0; c < K_NCLASS && c < max; c++) {
+    // (late_out, the last class, is listed for handles that had the late output on: the list of every
+    // other handle is what it was before the class existed)
+    const int nclass = h->lo_listed ? K_NCLASS : K_NCLASS - 1;
+    static_assert(K_LATE_OUT == K_NCLASS - 1, "late_out is the last class");
+    *count = nclass;
+    for (int c = 0; c < nclass && c < max; c++) {
         std::memset(&out[c], 0, sizeof(fg_kernel_stat));
         std::snprintf(out[c].name, sizeof out[c].name, "%s", kClassName[c]);
         out[c].launches = h->kstat[c].launches;

@@ -52,6 +52,23 @@ __host__ __device__ __forceinline__ LateClass late_class(const WindowSpec& w, in
     return c;
 }
 
+// k_late_split's `regular` condition: the element takes the regular ingest (all of them when
+// nothing is late-allowed; under a PurgingTrigger also the late-allowed ones whose last window has
+// not fired -- that window still collects them)
+__host__ __device__ __forceinline__ bool ds_regular(const LateClass& c, bool purging) {
+    return !c.late_allowed || (purging && !c.last_fired);
+}
+// The element ends in the ingest's drop count (isSkippedElement && isElementLate,
+// WindowOperator.processElement :448-456): it reaches the regular ingest -- no allowed lateness, or
+// k_late_split's `regular` -- and classify's target_slice refuses it there, at the ingest's own
+// progress (Long.MIN_VALUE after a restore: nothing is dropped until the first watermark).
+__host__ __device__ __forceinline__ bool ds_dropped(const WindowSpec& w, int64_t ts, int64_t progress, int64_t late_wm,
+                                                    int64_t lateness, bool purging) {
+    if (lateness != 0 && !ds_regular(late_class(w, ts, late_wm, lateness), purging)) return false;
+    int64_t target;
+    return !target_slice(w, ts, progress, &target);
+}
+
 struct LateSplit {
     WindowSpec w;
     int64_t wm;
@@ -122,6 +139,32 @@ struct LateRound {
     unsigned long long* out_count;
     int64_t out_cap;
 };
+
+// Late-element side output (fg_set_late_output, fg_late_out.hip): the batch's dropped elements
+// (ds_dropped) appended, in arrival order, to the handle's late-record columns.
+constexpr int kLateOutChunk = 4096;   // elements per workgroup of the count and scatter passes
+struct LateOut {
+    WindowSpec w;
+    int64_t progress;             // the ingest's progress (IngestParams.progress)
+    int64_t late_wm;              // late_split's watermark
+    int64_t lateness;
+    int32_t purging;
+    int32_t n_chunks;
+    int64_t n;
+    const int64_t* key;
+    const int64_t* ts;
+    const int64_t* val;           // NULL: no value column
+    const uint8_t* vnull;         // NULL: no NULL flags (0 is written)
+    uint32_t* chunk_cnt;          // [n_chunks] dropped elements per chunk
+    unsigned long long* chunk_base;   // [n_chunks] position of the chunk's first late record
+    unsigned long long* total;    // [0] records not yet collected, [1] records that found no room
+    int64_t cap;                  // records the columns hold
+    int64_t* o_key;
+    int64_t* o_ts;
+    int64_t* o_val;
+    uint8_t* o_null;
+};
+hipError_t launch_late_out(const LateOut& p, hipStream_t s);   // count, scan, scatter
 
 hipError_t launch_late_split(const LateSplit& p, hipStream_t s);
 hipError_t launch_late_reset(const LateRound& p, hipStream_t s);   // claim table, flags, nsel

@@ -105,7 +105,7 @@ __global__ __launch_bounds__(kLateThreads) void k_late_split(LateSplit p) {
     const uint8_t nul = p.vnull ? p.vnull[i] : 0;
     const LateClass c = late_class(p.w, ts, p.wm, p.lateness);
     const bool late = valid && c.late_allowed;
-    const bool regular = valid && (!c.late_allowed || (p.purging && !c.last_fired));
+    const bool regular = valid && ds_regular(c, p.purging != 0);
     const unsigned long long at_l = wave_reserve(&p.counts[0], late ? 1u : 0u);
     const unsigned long long at_r = wave_reserve(&p.counts[1], regular ? 1u : 0u);
     if (late) {

@@ -116,7 +116,9 @@ class DataStreamWindowOperator:
 
     def __init__(self, kind: str, size: int, slide: int = 0, offset: int = 0, val_type: str = "i64",
                  agg: str = "sum", allowed_lateness: int = 0, purging: bool = False, api: str = "reduce",
-                 **engine):
+                 late_output: bool = False, **engine):
+        """late_output: WindowedStream.sideOutputLateData(tag) -- late elements are returned by
+        late_records() after each process_batch instead of being counted in late_dropped."""
         if api == "reduce" and agg not in ("sum", "min", "max"):
             raise ValueError(f"aggregation {agg!r}: sum, min or max (minBy / maxBy: min / max)")
         if api == "aggregate" and agg not in ("count", "sum", "avg", "min", "max"):
@@ -133,9 +135,13 @@ class DataStreamWindowOperator:
         self._engine_kw = dict(engine)
         win = tumbling(size, offset) if kind == "tumble" else hopping(size, slide, offset)
         aggs = ("count_star",) + ((self.vkind,) if self.vkind else ())
-        self.op = WindowAggOperator(win, aggs=aggs, val_type=val_type if self.vkind else "none",
+        self.late_output = bool(late_output)
+        # (COUNT reads no field; with the side output the engine still takes it: a late element
+        # leaves as the Tuple2 it came in as)
+        self._takes_val = bool(self.vkind) or self.late_output
+        self.op = WindowAggOperator(win, aggs=aggs, val_type=val_type if self._takes_val else "none",
                                     mode="datastream", allowed_lateness=allowed_lateness,
-                                    purging_trigger=purging, **engine)
+                                    purging_trigger=purging, late_output=self.late_output, **engine)
         self.watermark = JMIN
         self.restored = {}   # window end -> dict(key, value, pending) of restored (key, window) entries
 
@@ -144,7 +150,18 @@ class DataStreamWindowOperator:
 
     # -- processElement / processWatermark ----------------------------------------------------
     def process_batch(self, key, ts, val):
-        self.op.process_batch(key, ts, val if self.vkind else None)   # (COUNT reads no field)
+        self.op.process_batch(key, ts, val if self._takes_val else None)   # (COUNT reads no field)
+
+    def late_records(self) -> np.ndarray:
+        """The side output of the batches since the last call (WindowOperator.sideOutput,
+        processElement :448-456), in arrival order: (key, value bits, timestamp = the element's).
+        A shim emits them under the lateDataOutputTag after each batch, and in any case before it
+        forwards a watermark."""
+        r = self.op.collect_late()
+        out = np.zeros(len(r["key"]), dtype=[("key", "<i8"), ("value", "<i8"), ("timestamp", "<i8")])
+        out["key"], out["timestamp"] = r["key"], r["rowtime"]
+        out["value"] = np.ascontiguousarray(r["val"]).view(np.int64)
+        return out
 
     def _cleanup_time(self, end):
         """WindowOperator.cleanupTime (:669-673): maxTimestamp + allowedLateness, Long.MAX_VALUE

@@ -84,8 +84,13 @@ class WindowAggOperator:
                  buffer_records: int = 1 << 22, device: int = 0, max_parallelism: int = 128,
                  key_group_range=(0, 127), kernel_timing: bool = False, local_partials: bool = False,
                  proctime: bool = False, zone: str | None = None, windowed: bool = False,
-                 allowed_lateness: int = 0, purging_trigger: bool = False, fired_runs: bool = False):
+                 allowed_lateness: int = 0, purging_trigger: bool = False, fired_runs: bool = False,
+                 late_output: bool = False):
         """fired_runs: run mode (fg_set_fired_runs, see set_fired_runs).
+
+        late_output (DataStream): WindowedStream.sideOutputLateData -- late elements are kept and
+        returned by collect_late() instead of being counted (fg_set_late_output, see
+        set_late_output).
 
         allowed_lateness (DataStream): WindowedStream.allowedLateness -- a fired window keeps
         its state until maxTimestamp + allowed_lateness, and an element reaching it meanwhile
@@ -163,12 +168,14 @@ class WindowAggOperator:
         self._dev_rows_ref = C.byref(self._dev_rows)
         self._lib = lib
         self._runs_on = False
-        if fired_runs:
-            try:
+        try:
+            if fired_runs:
                 self.set_fired_runs(True)
-            except Exception:
-                self.close()
-                raise
+            if late_output:
+                self.set_late_output(True)
+        except Exception:
+            self.close()
+            raise
 
     # -- lifecycle -------------------------------------------------------------------------
     def close(self):
@@ -417,6 +424,50 @@ class WindowAggOperator:
                 return np.zeros(0, dtype=np.int64)
             return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_int64)), shape=(n,)).copy()
         return {k: col(getattr(rr, k)) for k in RUN_COLUMNS}
+
+    # -- late elements as a side output -----------------------------------------------------------
+    def set_late_output(self, on: bool = True):
+        """fg_set_late_output (WindowedStream.sideOutputLateData): while on, every element the
+        operator would count in num_late_records_dropped is kept instead and returned by
+        collect_late(); the counter does not move. DataStream operators only (WindowSpecError
+        otherwise); turning it off with uncollected records is refused (FlinkGpuError, FG_ESTATE)."""
+        L.check(self._lib.fg_set_late_output(self._h, 1 if on else 0), self._h)
+
+    def collect_late(self, host: bool = True) -> dict:
+        """fg_collect_late: the late elements of the batches since the last collect, in arrival
+        order, as columns key, rowtime (int64), val (int64 / float64 per val_type; None without
+        a value column) and val_null (uint8, all 0 when no batch carried NULL flags). host=True:
+        numpy arrays copied out by the library; host=False: device tensors over the library's
+        columns, valid until the next call on this operator that takes a batch."""
+        r = L.FgLateRecords()
+        L.check(self._lib.fg_collect_late(self._h, L.HOST if host else L.DEVICE, C.byref(r)), self._h)
+        n = int(r.n)
+        vdt = np.float64 if self.val_type == L.VAL_F64 else np.int64
+        if host:
+            def col(p, dt):
+                if n == 0:
+                    return np.zeros(0, dtype=dt)
+                ct = C.c_uint8 if dt is np.uint8 else C.c_int64
+                return np.ctypeslib.as_array(C.cast(p, C.POINTER(ct)), shape=(n,)).copy().view(dt)
+            return {"key": col(r.key, np.int64), "rowtime": col(r.rowtime, np.int64),
+                    "val": None if self.val_type == L.VAL_NONE else col(r.val, vdt),
+                    "val_null": col(r.val_null, np.uint8) if r.val_null else np.zeros(n, dtype=np.uint8)}
+        import torch
+        dev = torch.device("cuda", self.cfg.device_id)
+
+        class _Col:
+            def __init__(self, ptr, typestr):
+                self.__cuda_array_interface__ = {"shape": (n,), "typestr": typestr, "data": (int(ptr), False),
+                                                 "version": 2}
+
+        def dcol(p, typestr, dt):
+            if n == 0 or not p:
+                return torch.zeros(n, dtype=dt, device=dev)
+            return torch.as_tensor(_Col(p, typestr), device=dev)
+        return {"key": dcol(r.key, "<i8", torch.int64), "rowtime": dcol(r.rowtime, "<i8", torch.int64),
+                "val": None if self.val_type == L.VAL_NONE else
+                dcol(r.val, "<f8" if vdt is np.float64 else "<i8", torch.float64 if vdt is np.float64 else torch.int64),
+                "val_null": dcol(r.val_null, "|u1", torch.uint8)}
 
     def rows_to_host(self, r: L.FgRows) -> np.ndarray:
         """Host copy of device FgRows (process_watermark(device_output=True) / collect_fired) in the

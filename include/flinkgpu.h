@@ -30,6 +30,8 @@
  *   HeapSnapshotStrategy / KeyGroupRangeOffsets (a keyed snapshot written in key-group order
  *     with an offset per key group)                  fg_set_snapshot_grouping, fg_snapshot_key_groups
  *   SlicingWindowOperator.getNumLateRecordsDropped :300-303            fg_late_dropped
+ *   WindowedStream.sideOutputLateData -> WindowOperator.processElement :448-456
+ *     (sideOutput(element) instead of numLateRecordsDropped.inc())      fg_set_late_output, fg_collect_late
  *   two-phase: LocalAggCombiner.combine (local operator output)        fg_config.flags |= FG_FLAG_LOCAL_PARTIALS
  *     GlobalAggCombiner.combine  .../combines/GlobalAggCombiner.java:77-110  fg_add_partials
  *   WindowBuffer.close / SlicingWindowOperator.close :178-183           fg_close
@@ -438,6 +440,48 @@ typedef struct fg_row_runs {
 } fg_row_runs;
 int  fg_set_fired_runs(fg_handle* h, int32_t on);
 int  fg_fired_runs(fg_handle* h, fg_row_runs* out);
+/* Late elements as a side output (ABI 16, added; WindowedStream.sideOutputLateData): in
+ * WindowOperator.processElement (:448-456) an element whose windows are all late and which is late
+ * itself is emitted to the side output when a lateDataOutputTag is set, and only otherwise counted in
+ * numLateRecordsDropped. fg_set_late_output(h, on != 0) selects the first branch, 0 the second (the
+ * default). Idempotent.
+ *  - FG_EINVAL (turning on): a handle that is not FG_MODE_DATASTREAM, or one with FG_FLAG_LOCAL_PARTIALS,
+ *    FG_FLAG_PROCTIME or FG_FLAG_WINDOWED -- SQL window operators have no side output.
+ *  - FG_ESTATE (turning off): late records are not collected yet.
+ *    fg_last_error names the reason. The handle stays usable after either error.
+ * While on, every element that the same handle with the mode off would add to fg_late_dropped is kept
+ * as a record instead, through fg_add_batch (every fg_batch_format) and fg_add_rows alike, and
+ * fg_late_dropped does not move (the reference increments the counter only in the else branch). Fired
+ * rows, state, snapshots, records_in and every other statistic are what they are with the mode off.
+ * The records are copied out on the device by a pass of their own ahead of the ingest
+ * (fg_kernel_stats class "late_out": records = the batches' elements, rows = the late records; the
+ * class follows every other class, and fg_kernel_stats lists it for a handle once the mode was turned
+ * on); the host reads nothing during fg_add_batch.
+ * fg_collect_late: the late records of all batches since the previous collect (or since fg_open,
+ * fg_reset, fg_restore*), in arrival order -- batch by batch, inside a batch by index, as the reference
+ * emits them one by one in processElement. rowtime is the element's timestamp as it was handed in
+ * (widened to 8 bytes), val its value bits. FG_HOST copies the columns into library-owned host memory;
+ * FG_DEVICE returns device columns, complete in stream order on fg_stream. The call drains the list: a
+ * second call returns n = 0. The columns stay valid until the next fg_add_batch / fg_add_rows /
+ * fg_collect_late / fg_reset / fg_restore* / fg_close on the handle.
+ *  - FG_ESTATE: the mode is off; or "internal: late output and ingest disagree" -- the number of
+ *    records kept differs from the ingest's own drop count (the list is drained, nothing is returned).
+ * Late records are not operator state (the reference has emitted them when processElement returns):
+ * snapshots do not contain them, fg_reset and fg_restore* discard uncollected ones. A shim therefore
+ * collects after each batch, and in any case before it forwards a watermark or takes a checkpoint
+ * barrier. The columns grow with the uncollected records: 24 B + 1 B per element of the largest
+ * uncollected run of batches, as a worst case. */
+typedef struct fg_late_records {
+    int64_t n;
+    int32_t location;          /* fg_location of the columns */
+    int32_t reserved0;
+    const int64_t* key;
+    const int64_t* rowtime;    /* the element's timestamp as it was handed in (8-byte, widened) */
+    const void*    val;        /* int64_t[] / double[] bits; NULL for FG_VAL_NONE */
+    const uint8_t* val_null;   /* NULL when no batch since the last collect carried val_null */
+} fg_late_records;
+int  fg_set_late_output(fg_handle* h, int32_t on);
+int  fg_collect_late(fg_handle* h, int32_t out_location, fg_late_records* out);
 /* Selective images (ABI 16, added): a checkpoint that exports and copies only the slices its caller
  * needs. The engine says what is resident and what changed (plan), the caller answers with a mask
  * (a shim's policy needs more than the changed slices: a CUMULATE namespace is rebuilt from all its

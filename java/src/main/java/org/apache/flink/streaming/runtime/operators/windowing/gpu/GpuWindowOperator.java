@@ -62,6 +62,7 @@ import org.apache.flink.streaming.runtime.streamrecord.StreamRecord;
 import org.apache.flink.table.runtime.operators.window.gpu.FgConfig;
 import org.apache.flink.table.runtime.operators.window.gpu.FlinkGpu;
 import org.apache.flink.table.runtime.operators.window.gpu.GpuWindowAggSpec;
+import org.apache.flink.util.OutputTag;
 
 import java.io.Serializable;
 import java.nio.ByteBuffer;
@@ -186,6 +187,13 @@ public final class GpuWindowOperator<V, ACC, OUT> extends AbstractStreamOperator
     private final boolean isDouble;
     private final boolean hasValue;
     private final boolean purging;
+    /**
+     * WindowedStream.sideOutputLateData(tag): late elements go to this side output instead of
+     * numLateRecordsDropped (WindowOperator.processElement :448-456); null: they are counted.
+     */
+    private OutputTag<Tuple2<Long, V>> lateDataOutputTag;
+    /** f1 crosses to the engine: it aggregates it, or returns it with a late element */
+    private boolean takesValue;
 
     private transient long handle;
     /** the handle is in run mode (FgConfig.firedRuns): fired rows carry no window columns */
@@ -261,6 +269,22 @@ public final class GpuWindowOperator<V, ACC, OUT> extends AbstractStreamOperator
         this.inputType = inputType;
         this.acc = acc;
         this.purging = (spec.flags & FgConfig.FLAG_PURGING_TRIGGER) != 0;
+        this.takesValue = hasValue;
+    }
+
+    /**
+     * WindowedStream.sideOutputLateData: the engine keeps the late elements (fg_set_late_output,
+     * turned on at open) and the operator emits them under the tag after each batch, in arrival
+     * order and before the next watermark is forwarded. A COUNT then hands f1 to the engine too,
+     * so that a late element leaves as the Tuple2 it came in as.
+     */
+    public GpuWindowOperator<V, ACC, OUT> sideOutputLateData(OutputTag<Tuple2<Long, V>> lateDataOutputTag) {
+        this.lateDataOutputTag = lateDataOutputTag;
+        this.takesValue = hasValue || lateDataOutputTag != null;
+        if (takesValue) {
+            spec.valType = isDouble ? FgConfig.VAL_F64 : FgConfig.VAL_I64;
+        }
+        return this;
     }
 
     @Override
@@ -295,9 +319,12 @@ public final class GpuWindowOperator<V, ACC, OUT> extends AbstractStreamOperator
         if (firedRuns) {
             FlinkGpu.setFiredRuns(handle, true);
         }
+        if (lateDataOutputTag != null) {
+            FlinkGpu.setLateOutput(handle, true);
+        }
         keys = direct(8L * spec.batchRecords);
         timestamps = direct(8L * spec.batchRecords);
-        vals = hasValue ? direct(8L * spec.batchRecords) : null;
+        vals = takesValue ? direct(8L * spec.batchRecords) : null;
         currentWatermark = Long.MIN_VALUE;
         restored = new TreeMap<>();
         imageWindows = new HashSet<>();
@@ -324,7 +351,7 @@ public final class GpuWindowOperator<V, ACC, OUT> extends AbstractStreamOperator
     public void processElement(StreamRecord<Tuple2<Long, V>> element) throws Exception {
         keys.putLong(8 * count, element.getValue().f0);
         timestamps.putLong(8 * count, element.getTimestamp());
-        if (hasValue) {
+        if (takesValue) {
             vals.putLong(8 * count, bitsOf(element.getValue().f1));
         }
         if (++count == spec.batchRecords) {
@@ -336,6 +363,26 @@ public final class GpuWindowOperator<V, ACC, OUT> extends AbstractStreamOperator
         if (count > 0) {
             FlinkGpu.addBatch(handle, keys, timestamps, vals, null, count);
             count = 0;
+            if (lateDataOutputTag != null) {
+                sideOutputLate();
+            }
+        }
+    }
+
+    /**
+     * The batch's late elements (fg_collect_late: [n, key[n], rowtime[n], valBits[n], null[n]]), one
+     * by one in arrival order as WindowOperator.sideOutput emits them; every caller of flushBatch
+     * runs this before it forwards a watermark or takes a barrier.
+     */
+    @SuppressWarnings("unchecked")
+    private void sideOutputLate() {
+        long[] late = FlinkGpu.collectLate(handle);
+        int n = (int) late[0];
+        for (int i = 0; i < n; i++) {
+            long bits = late[1 + 2 * n + i];
+            V f1 = (V) (isDouble ? (Object) Double.longBitsToDouble(bits) : (Object) bits);
+            long rowtime = late[1 + n + i];
+            output.collect(lateDataOutputTag, new StreamRecord<>(Tuple2.of(late[1 + i], f1), rowtime));
         }
     }
 
@@ -412,9 +459,11 @@ public final class GpuWindowOperator<V, ACC, OUT> extends AbstractStreamOperator
             }
         }
         currentWatermark = Math.max(currentWatermark, wm);
-        long dropped = FlinkGpu.lateDropped(handle);
-        numLateRecordsDropped.inc(dropped - droppedSeen);
-        droppedSeen = dropped;
+        if (lateDataOutputTag == null) {   // (the reference counts only what it does not side-output)
+            long dropped = FlinkGpu.lateDropped(handle);
+            numLateRecordsDropped.inc(dropped - droppedSeen);
+            droppedSeen = dropped;
+        }
         super.processWatermark(mark);
     }
 

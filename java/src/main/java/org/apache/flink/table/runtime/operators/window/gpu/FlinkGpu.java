@@ -104,6 +104,22 @@ public final class FlinkGpu {
      */
     public static native long[] firedRuns(long h);
 
+    /**
+     * fg_set_late_output (ABI 16): WindowedStream.sideOutputLateData -- every element the handle
+     * would count in {@link #lateDropped} is kept instead and returned by {@link #collectLate}; the
+     * counter does not move. DataStream handles only (IllegalArgumentException otherwise); turning
+     * it off with uncollected records is refused.
+     */
+    public static native void setLateOutput(long h, boolean on);
+
+    /**
+     * fg_collect_late: the late elements of the batches since the last collect, in arrival order,
+     * as [n, key[n], rowtime[n], valBits[n], null[n]]: valBits the value's long or the double's
+     * bits (0 without a value column), null 1 for a NULL value. Drains the list. Called after each
+     * batch, and in any case before a watermark is forwarded or a barrier taken.
+     */
+    public static native long[] collectLate(long h);
+
     /** fg_flush (prepareSnapshotPreBarrier). */
     public static native void flush(long h);
 

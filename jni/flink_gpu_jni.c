@@ -20,6 +20,8 @@
  *                   and its host copy queued; the shim clears the previous image meanwhile)
  *   restore         fg_restore           (initializeState)
  *   lateDropped     fg_late_dropped      (numLateRecordsDropped)
+ *   setLateOutput / collectLate   fg_set_late_output / fg_collect_late (sideOutputLateData: late elements
+ *                   returned in arrival order instead of counted)
  *   close           fg_close
  *   dict*           fg_key_dict_*        (BinaryRowDataKeySelector rows of any key type)
  *   hostRegister    fg_host_register     (page-lock a managed-memory segment at open: direct DMA)
@@ -285,6 +287,41 @@ JNIEXPORT jlongArray JNICALL FN(firedRuns)(JNIEnv* env, jclass cls, jlong hp) {
         (*env)->SetLongArrayRegion(env, out, 1 + n, n, (const jlong*)r.window_end);
         (*env)->SetLongArrayRegion(env, out, 1 + 2 * n, n, (const jlong*)r.first_row);
         (*env)->SetLongArrayRegion(env, out, 1 + 3 * n, n, (const jlong*)r.rows);
+    }
+    return out;
+}
+
+/* void setLateOutput(long h, boolean on): WindowedStream.sideOutputLateData (fg_set_late_output, ABI 16)
+ * -- late elements are kept for collectLate instead of being counted in lateDropped */
+JNIEXPORT void JNICALL FN(setLateOutput)(JNIEnv* env, jclass cls, jlong hp, jboolean on) {
+    (void)cls;
+    fg_handle* h = (fg_handle*)(intptr_t)hp;
+    (void)check(env, h, fg_set_late_output(h, on ? 1 : 0));
+}
+
+/* long[] collectLate(long h): the late elements of the batches since the last collect, in arrival
+ * order (fg_collect_late FG_HOST), as one array: [n, key[n], rowtime[n], valBits[n], null[n]] -- valBits
+ * the value's long / the double's bits (0 without a value column), null 1 for a NULL value. */
+JNIEXPORT jlongArray JNICALL FN(collectLate)(JNIEnv* env, jclass cls, jlong hp) {
+    (void)cls;
+    fg_handle* h = (fg_handle*)(intptr_t)hp;
+    fg_late_records r;
+    if (check(env, h, fg_collect_late(h, FG_HOST, &r))) return NULL;
+    const jsize n = (jsize)r.n;
+    jlongArray out = (*env)->NewLongArray(env, 1 + 4 * n);   /* (zero-filled) */
+    if (!out) return NULL;
+    const jlong head = n;
+    (*env)->SetLongArrayRegion(env, out, 0, 1, &head);
+    if (n > 0) {
+        (*env)->SetLongArrayRegion(env, out, 1, n, (const jlong*)r.key);
+        (*env)->SetLongArrayRegion(env, out, 1 + n, n, (const jlong*)r.rowtime);
+        if (r.val) (*env)->SetLongArrayRegion(env, out, 1 + 2 * n, n, (const jlong*)r.val);
+        if (r.val_null) {
+            for (jsize i = 0; i < n; i++) {
+                const jlong f = r.val_null[i];
+                if (f) (*env)->SetLongArrayRegion(env, out, 1 + 3 * n + i, 1, &f);
+            }
+        }
     }
     return out;
 }
