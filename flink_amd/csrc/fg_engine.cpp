@@ -2936,9 +2936,9 @@ int grow_acc(fg_handle* h, int64_t need) {
 }
 
 // one global-phase pass over partial accumulator rows (device columns; `ts` = the pseudo
-// rowtime slice_end - 1 - tz): count pass with the global operator's late rules, then
-// the rows are scattered into their slice lanes' accumulator areas. Returns -1 when the
-// rows span more slices than the lanes can hold.
+// rowtime, each row's slice start: pseudo_rowtime, fg_window.h): count pass with the global
+// operator's late rules, then the rows are scattered into their slice lanes' accumulator
+// areas. Returns -1 when the rows span more slices than the lanes can hold.
 int acc_pass(fg_handle* h, int64_t n, const int64_t* key, const int64_t* ts, const int64_t* cs, const int64_t* cv,
              const int64_t* sum, const int64_t* v1, const int64_t* v2, int64_t flo, int64_t fhi, bool count_drops,
              Counters* out) {
@@ -3935,8 +3935,7 @@ int fg_add_batch(fg_handle* h, const fg_batch* b) {
         HIPCHK(h, h->in_wts.ensure(8 * n + 8));
         unsigned long long* bad = reinterpret_cast<unsigned long long*>(h->in_wts.as<int64_t>() + n);
         HIPCHK(h, hipMemsetAsync(bad, 0, 8, h->stream));
-        HIPCHK(h, launch_window_end_rowtime(ts, n, h->w.tz, h->w.slice, h->slice_phase, h->in_wts.as<int64_t>(), bad,
-                                            h->stream));
+        HIPCHK(h, launch_window_end_rowtime(ts, n, h->w, h->slice_phase, h->in_wts.as<int64_t>(), bad, h->stream));
         HIPCHK(h, hipMemcpyAsync(h->h_counters.p, bad, 8, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
         unsigned long long nbad = 0;
@@ -4121,9 +4120,12 @@ static int add_partials(fg_handle* h, const fg_partials* b) {
     }
     HIPCHK(h, h->in_ts.ensure(8 * n));
     int64_t* ts = h->in_ts.as<int64_t>();
-    // fixed offset: pseudo rowtime slice_end - 1 - tz; zone rules: slice_end - 1 in local
-    // time, assigned without the zone shift (WindowSpec::local_input, set in acc_pass)
-    HIPCHK(h, launch_pseudo_rowtime(se, n, h->w.tz_n > 0 ? 0 : h->w.tz, ts, h->stream));
+    // the slice's start as the pseudo rowtime (pseudo_rowtime, fg_window.h): an epoch time under
+    // a fixed offset; with zone rules a local time, assigned without the zone shift
+    // (WindowSpec::local_input, as acc_pass sets it)
+    WindowSpec pw = h->w;
+    pw.local_input = h->w.tz_n > 0 ? 1 : 0;
+    HIPCHK(h, launch_pseudo_rowtime(se, n, pw, ts, h->stream));
     h->records_in += n;
     int rc0 = seed_anchor(h, ts, nullptr);
     if (rc0) return rc0;
@@ -4179,22 +4181,37 @@ static int advance_progress(fg_handle* h, int64_t wm) {
     const FireRange fr{prev, wm};
     const FireRange* fuse = wm > prev ? &fr : nullptr;
     if (h->local) {
-        // LocalSlicingWindowAggOperator.processWatermark (:113-139): once the watermark fires
-        // the smallest buffered slice, the combiner emits partial accumulators; here every
-        // fired slice lane emits its partials, and slices flushed earlier to make room are
-        // emitted from their tables
+        // LocalSlicingWindowAggOperator.processWatermark (:121-134): a watermark that advances
+        // and passes the next trigger (getNextTriggerWatermark: the offset-0 grid of the slice
+        // interval) flushes the buffer once it fires the smallest buffered slice, and the combiner
+        // emits partial accumulators. Between two triggers nothing leaves, late records of fired
+        // slices included: the global operators count late drops per partial row, so the rows
+        // leave when the reference's do. Here every fired slice lane emits its partials, and
+        // slices flushed earlier to make room are emitted from their tables; the slices not fired
+        // yet stay staged -- their partials would arrive in time either way.
+        // With a window offset off the slice grid that no longer holds: a slice's timer falls
+        // between two triggers, its partials leave behind it, and the early partials of the slices
+        // after it, which leave with them, are the ones the global operators still accept. There
+        // the whole buffer is flushed, as the reference's is.
         // (fg_flush_partials: prepareSnapshotPreBarrier -> RecordsWindowBuffer.flush, every
         // buffered slice emits its partials now, the local operator keeps no state)
-        const bool every = h->local_emit_all;
+        bool every = h->local_emit_all, flush_now = false;
+        if (!every && wm > h->current_progress && wm >= h->next_trigger) {
+            h->next_trigger = next_trigger_watermark(h->w, wm, h->w.slice);
+            int64_t min_end = min_staged_slice_end(h);   // (JMAX: nothing staged)
+            if (!h->tables.empty()) min_end = std::min(min_end, h->tables.begin()->first);
+            flush_now = is_window_fired(h->w, min_end, wm);
+            every = flush_now && h->slice_phase != 0;
+        }
         if (wm > h->current_progress) h->current_progress = wm;
-        if (staged_any(h) && (every || is_window_fired(h->w, min_staged_slice_end(h), wm))) {
+        if (staged_any(h) && (every || flush_now)) {
             const FireRange all{JMIN, every ? JMAX : wm};
             rc = flush(h, &all, !every);
             if (rc) return rc;
         }
         std::vector<int64_t> ends;
         for (auto& kv : h->tables)
-            if (every || is_window_fired(h->w, kv.first, wm)) ends.push_back(kv.first);
+            if (every || (flush_now && is_window_fired(h->w, kv.first, wm))) ends.push_back(kv.first);
         for (int64_t e : ends) {
             rc = fire_one(h, e, {h->tables[e].get()}, nullptr);
             if (rc) return rc;
@@ -4206,8 +4223,16 @@ static int advance_progress(fg_handle* h, int64_t wm) {
             h->arrival_progress = h->current_progress;   // the staged records arrived under it
             h->current_progress = wm;
             if (h->current_progress >= h->next_trigger) {
+                // RecordsWindowBuffer.flush empties the whole buffer. Slices not fired yet stay
+                // staged here all the same while the slice grid is the trigger grid (offset 0): the
+                // watermark that fires them passes a trigger and flushes them first. With a window
+                // offset off the slice grid a slice's timer falls between two triggers: its records
+                // must be in state by then, and the records that reach the buffer afterwards are
+                // flushed behind the timer, into state no timer fires any more -- the reference
+                // loses them, and so does this: every staged slice is flushed.
+                const bool off_grid = h->slice_phase != 0;
                 if (staged_any(h) && is_window_fired(h->w, min_staged_slice_end(h), wm)) {
-                    rc = flush(h, fuse, true);
+                    rc = flush(h, fuse, !off_grid);
                     if (rc) return rc;
                 }
                 h->next_trigger = next_trigger_watermark(h->w, wm, h->w.slice);
@@ -4251,7 +4276,8 @@ static int advance_progress(fg_handle* h, int64_t wm) {
 // fire pending, fg_advance_progress_async takes only its progress bookkeeping -- the fire's
 // completion is left to the call that needs it, so the host does not wait for the fire here.
 // true when a window end on the slice grid may have its timer in (prev, wm]: exact for zones
-// without rules (trigger_time(e) = e - 1 - tz, increasing in e), assumed otherwise
+// without rules (the trigger time of an end, its last millisecond as an epoch time, increases
+// with the end), assumed otherwise
 static bool trigger_between(const fg_handle* h, int64_t prev, int64_t wm) {
     const WindowSpec& w = h->w;
     if (wm <= prev) return false;

@@ -358,8 +358,8 @@ struct ExportSelParams {
 hipError_t launch_export_sel(const ExportSelParams& p, hipStream_t s);
 
 hipError_t launch_ingest_count(const IngestParams& p, hipStream_t s);
-// global phase: rowtime = slice_end - 1 - tz for partial rows; scatter of accumulator rows
-hipError_t launch_pseudo_rowtime(const int64_t* slice_end, int64_t n, int64_t tz, int64_t* out, hipStream_t s);
+// global phase: rowtime = pseudo_rowtime(w, slice_end) for partial rows; scatter of accumulator rows
+hipError_t launch_pseudo_rowtime(const int64_t* slice_end, int64_t n, const WindowSpec& w, int64_t* out, hipStream_t s);
 // a few words stored by a kernel (scratch counters initialised in stream order: a small
 // host-to-device copy costs a blit plus ~20 us of queue latency before the next kernel)
 struct Words16 {
@@ -372,7 +372,7 @@ hipError_t launch_publish_words(const unsigned long long* src, int32_t n, unsign
                                 unsigned long long seq, hipStream_t s);
 hipError_t launch_widen_columns(const int32_t* k32, const uint32_t* t32, const int32_t* v32, int64_t n, int64_t tbase,
                                 int64_t* key, int64_t* ts, int64_t* val, hipStream_t s);
-hipError_t launch_window_end_rowtime(const int64_t* wend, int64_t n, int64_t tz, int64_t S, int64_t phase,
+hipError_t launch_window_end_rowtime(const int64_t* wend, int64_t n, const WindowSpec& w, int64_t phase,
                                      int64_t* out, unsigned long long* off_grid, hipStream_t s);
 hipError_t launch_acc_scatter(const IngestParams& p, const AccColumns& a, hipStream_t s);
 // packed BinaryRowData fixed-length parts -> key / rowtime / value / NULL columns; bad[0]

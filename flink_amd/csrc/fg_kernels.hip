@@ -1126,14 +1126,13 @@ hipError_t launch_part2(const IngestParams& p, hipStream_t s) {
 // ----------------------------------------------------------------------------------------
 // global phase: partial accumulators (LocalAggCombiner rows) -> per-lane accumulator areas
 // ----------------------------------------------------------------------------------------
-// A partial row of slice `slice_end` is classified like a record with rowtime
-// slice_end - 1 - tz (the `sliced` assigner: assignSliceEnd = the row's window end,
-// SliceAssigners.java:494-533), so the late rules of the global operator apply unchanged.
-__global__ void k_pseudo_rowtime(const int64_t* slice_end, int64_t n, int64_t tz, int64_t* out) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t e = slice_end[i];
-        out[i] = e == JMAX ? JMAX : jsub(jsub(e, 1), tz);
-    }
+// A partial row of slice `slice_end` is classified like a record with the rowtime
+// pseudo_rowtime(w, slice_end), the start of that slice (fg_window.h; the `sliced` assigner:
+// assignSliceEnd = the row's window end, SliceAssigners.java:494-533), so the late rules of
+// the global operator apply unchanged.
+__global__ void k_pseudo_rowtime(const int64_t* slice_end, int64_t n, WindowSpec w, int64_t* out) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        out[i] = pseudo_rowtime(w, slice_end[i]);
 }
 
 // Packed BinaryRowData rows (BinaryRowData.java:68-76): the fixed-length part of row i at
@@ -1173,17 +1172,19 @@ hipError_t launch_rows_to_columns(const uint8_t* rows, int64_t n, const RowLayou
 }
 
 // Windowed input (WindowedSliceAssigner): the attached window_end of a row is its slice,
-// classified like a record with rowtime window_end - 1 - tz; ends off the inner assigner's
-// slice grid are counted (the caller fails loudly on any)
-__global__ void k_window_end_rowtime(const int64_t* wend, int64_t n, int64_t tz, int64_t S, int64_t phase,
+// classified like a record with the rowtime pseudo_rowtime(w, window_end), the start of that
+// slice (fg_window.h); ends off the inner assigner's slice grid are counted (the caller fails
+// loudly on any)
+__global__ void k_window_end_rowtime(const int64_t* wend, int64_t n, WindowSpec w, int64_t phase,
                                      int64_t* out, unsigned long long* off_grid) {
+    const int64_t S = w.slice;
     unsigned long long bad = 0;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const int64_t e = wend[i];
         int64_t r = jsub(e, phase) % S;
         if (r < 0) r += S;
         bad += (r != 0 || e == JMAX) ? 1ull : 0ull;
-        out[i] = jsub(jsub(e, 1), tz);
+        out[i] = pseudo_rowtime(w, e);
     }
     if (bad) atomicAdd(off_grid, bad);
 }
@@ -1206,11 +1207,11 @@ hipError_t launch_widen_columns(const int32_t* k32, const uint32_t* t32, const i
     return hipGetLastError();
 }
 
-hipError_t launch_window_end_rowtime(const int64_t* wend, int64_t n, int64_t tz, int64_t S, int64_t phase,
+hipError_t launch_window_end_rowtime(const int64_t* wend, int64_t n, const WindowSpec& w, int64_t phase,
                                      int64_t* out, unsigned long long* off_grid, hipStream_t s) {
     int64_t blocks = (n + 255) / 256;
     blocks = blocks > 8192 ? 8192 : (blocks < 1 ? 1 : blocks);
-    fg_launch(k_window_end_rowtime, dim3((unsigned)blocks), dim3(256), 0, s, wend, n, tz, S, phase, out, off_grid);
+    fg_launch(k_window_end_rowtime, dim3((unsigned)blocks), dim3(256), 0, s, wend, n, w, phase, out, off_grid);
     return hipGetLastError();
 }
 
@@ -1259,10 +1260,10 @@ hipError_t launch_run_mark(const unsigned long long* out_count, unsigned long lo
     return hipGetLastError();
 }
 
-hipError_t launch_pseudo_rowtime(const int64_t* slice_end, int64_t n, int64_t tz, int64_t* out, hipStream_t s) {
+hipError_t launch_pseudo_rowtime(const int64_t* slice_end, int64_t n, const WindowSpec& w, int64_t* out, hipStream_t s) {
     int64_t blocks = (n + 255) / 256;
     blocks = blocks > 8192 ? 8192 : (blocks < 1 ? 1 : blocks);
-    fg_launch(k_pseudo_rowtime, dim3((unsigned)blocks), dim3(256), 0, s, slice_end, n, tz, out);
+    fg_launch(k_pseudo_rowtime, dim3((unsigned)blocks), dim3(256), 0, s, slice_end, n, w, out);
     return hipGetLastError();
 }
 

@@ -71,9 +71,21 @@ struct WindowSpec {
     // the rowtime column already holds local (UTC-shifted) times: partial rows and windowed
     // rows carry their slice / window end, which the `sliced` / `windowed` assigners take as
     // is (SliceAssigners.java:407-412, :520-524) -- set for zone rules, whose local -> epoch
-    // mapping is not invertible (a fixed offset round-trips through slice_end - 1 - tz)
+    // mapping is not invertible (a fixed offset round-trips through pseudo_rowtime below)
     int32_t local_input;
 };
+
+// The rowtime under which a row that carries its slice (or window) end `e` is classified.
+// The `sliced` / `windowed` assigners take e as it is (SliceAssigners.java:402-412, :494-533);
+// here such a row goes through assign_slice_end like a record, so it gets the start of its
+// own slice as epoch time, e - slice - tz (local_input: e - slice). That time is on the slice
+// grid -- remainder 0 under Java's truncated `%` on both sides of zero -- so
+// assign_slice_end gives e back for every end that does not wrap at Long.MIN_VALUE, and
+// rowtime + tz - tbase stays a multiple of the slice for the 32-bit fast path.
+__host__ __device__ __forceinline__ int64_t pseudo_rowtime(const WindowSpec& w, int64_t e) {
+    if (e == JMAX) return JMAX;
+    return jsub(jsub(e, w.slice), w.local_input ? 0 : w.tz);
+}
 
 // the zone tables of the side this code runs on
 __host__ __device__ __forceinline__ const int64_t* zone_trans(const WindowSpec& w) {
