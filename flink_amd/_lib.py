@@ -119,6 +119,11 @@ class FgRestoreInfo(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("rows_in", "rows_kept", "slices", "state_regions")]
 
 
+class FgKeyDictStats(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in (
+        "live", "issued", "free_ordinals", "arena_bytes", "table_slots", "side_rows", "retired_total", "reserved0")]
+
+
 class FgKernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("launches", C.c_int64), ("total_ms", C.c_double),
                 ("records", C.c_int64), ("rows", C.c_int64)]
@@ -148,6 +153,7 @@ EXPORTS = (
     "fg_comm_set_key_dicts", "fg_key_dict_arena",
     "fg_key_dict_copy_arena", "fg_key_dict_size", "fg_key_dict_stream", "fg_key_dict_set_timing",
     "fg_key_dict_kernel_stats", "fg_key_dict_last_error", "fg_key_dict_close",
+    "fg_key_dict_get_stats", "fg_key_dict_retain",
     "fg_binaryrow_hash", "fg_host_register", "fg_host_unregister",
     "fg_comm_unique_id", "fg_comm_open", "fg_comm_exchange_columns", "fg_comm_exchange_partials",
     "fg_comm_exchange_fired", "fg_comm_exchange_flushed", "fg_comm_round_begin", "fg_comm_round_exchange",
@@ -279,6 +285,11 @@ def load():
         L.fg_set_late_output.argtypes = [P, C.c_int32]
         L.fg_collect_late.argtypes = [P, C.c_int32, C.POINTER(FgLateRecords)]
         L.fg_set_late_output.restype = L.fg_collect_late.restype = C.c_int
+    if hasattr(L, "fg_key_dict_retain"):   # (the same)
+        L.fg_key_dict_get_stats.argtypes = [P, C.POINTER(FgKeyDictStats)]
+        L.fg_key_dict_retain.argtypes = [P, C.c_int32, C.c_int32, C.POINTER(P), C.POINTER(C.c_int64),
+                                         C.POINTER(FgKeyDictStats)]
+        L.fg_key_dict_get_stats.restype = L.fg_key_dict_retain.restype = C.c_int
     L.fg_selftest.argtypes = [C.c_int32, C.c_char_p, C.c_int32]
     L.fg_selftest.restype = C.c_int
     L.fg_comm_bytes_sent.argtypes = [P]

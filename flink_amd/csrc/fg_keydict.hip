@@ -32,6 +32,10 @@
 // owner and gathers their key rows in the grouped order (the same k_rows_* pipeline on the caller's
 // stream, k_owner_byte_counts for the bytes per owner), and keydict_intern_packed (fg_keydict.h)
 // checks and scans the lengths an owner received (k_recv_lengths) and interns the rows.
+// An entry lasts until fg_key_dict_retain retires it: the caller lists the ids that still hold
+// state, every other entry leaves the table and the arena (k_retain_*), and k_dict_assign hands
+// the retired ordinals out again before it issues a fresh one -- the dictionary is bounded by the
+// keys alive at once, not by the keys ever seen.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -99,8 +103,10 @@ struct DictDev {
     int32_t* ent_len;    // [ids]
     uint64_t* ent_tag;   // [ids] tag (0: resolved on the host, not in the table)
     uint8_t* arena;
-    unsigned long long* counters;   // [0] ids, [1] arena bytes, [2] collisions, [3] bad rows, [4] pending rows,
-                                    // [5] entry bytes of the lookup's misses, [6] lookup misses
+    unsigned long long* counters;   // [0] ordinals issued, [1] arena bytes, [2] collisions, [3] bad rows, [4] pending
+                                    // rows, [5] entry bytes of the lookup's misses, [6] lookup misses, [7] free ordinals taken
+    const int64_t* free_ord;   // [nfree] ordinals a retain retired, ascending: reused before a fresh one is issued
+    uint64_t nfree;      // (0: every new key takes a fresh ordinal)
     uint64_t mask;       // cap - 1
     int32_t kg_bits;     // id = ordinal << kg_bits | key group
 };
@@ -430,7 +436,12 @@ __global__ __launch_bounds__(kDictThreads) void k_dict_assign(DictDev d, RowsIn 
         const uint64_t s = j < np ? pend.slot[j] : 0;
         const bool own = j < np && d.slot_row[s] == (uint32_t)i;
         const int32_t len = own ? in.len[i] : 0;
-        const unsigned long long ord = wave_reserve(&d.counters[0], own ? 1u : 0u);
+        // its ordinal: the next of the free list while one is left (counters[7] runs past nfree once
+        // the list is spent), else a fresh one -- one reservation per wave per counter
+        const unsigned long long fp = d.nfree ? wave_reserve(&d.counters[7], own ? 1u : 0u) : 0ull;
+        const bool reuse = own && fp < d.nfree;
+        const unsigned long long fresh = wave_reserve(&d.counters[0], own && !reuse ? 1u : 0u);
+        const unsigned long long ord = reuse ? (unsigned long long)d.free_ord[fp] : fresh;
         const unsigned long long at = wave_reserve(&d.counters[1], own ? (uint32_t)(8 + ((len + 7) & ~7)) : 0u);
         if (!own) continue;
         const int64_t id = (int64_t)(ord << d.kg_bits | (uint64_t)pend.kg[j]);
@@ -488,9 +499,9 @@ __global__ __launch_bounds__(kDictThreads) void k_dict_gather(DictDev d, int64_t
     const int64_t i = (int64_t)blockIdx.x * kDictThreads + threadIdx.x;
     if (i >= n) return;
     const uint64_t ord = (uint64_t)ids[i] >> d.kg_bits;
-    const bool ok = ids[i] >= 0 && (int64_t)ord < nids;
-    off_out[i] = ok ? d.ent_off[ord] : -1;
-    len_out[i] = ok ? d.ent_len[ord] : -1;
+    const int32_t len = ids[i] >= 0 && (int64_t)ord < nids ? d.ent_len[ord] : -1;   // (< 0: a retired ordinal)
+    off_out[i] = len >= 0 ? d.ent_off[ord] : -1;
+    len_out[i] = len >= 0 ? len : -1;
 }
 
 // ---- fg_key_dict_rows: the packed key rows of ids (the layout fg_key_dict_intern reads) ----
@@ -538,8 +549,9 @@ __global__ __launch_bounds__(kDictThreads) void k_rows_lengths(DictDev d, int64_
     const bool valid = i < n;
     const int64_t id = valid ? ids[i] : 0;
     const uint64_t ord = (uint64_t)id >> d.kg_bits;
-    const bool ok = valid && id >= 0 && (int64_t)ord < nids;
-    const int32_t len = ok ? d.ent_len[ord] : 0;
+    const int32_t elen = valid && id >= 0 && (int64_t)ord < nids ? d.ent_len[ord] : -1;
+    const bool ok = elen >= 0;   // (a retired ordinal's length is -1: unknown, like one never issued)
+    const int32_t len = ok ? elen : 0;
     if (valid) len_out[i] = ok ? len : -1;
     const unsigned long long badm = __ballot(valid && !ok);   // (one atomic pair per wave holding a bad id)
     if (badm && (threadIdx.x & 63) == 0) {
@@ -666,6 +678,152 @@ __global__ __launch_bounds__(kDictThreads) void k_slots_clear(Slot* p, int64_t n
     }
 }
 
+// ---- fg_key_dict_retain: keep the listed ids, retire every other entry, compact, reuse ----
+//
+// Mark (k_retain_mark, one launch per set of ids: every id checked, a byte per kept ordinal), plan
+// (k_retain_sums + k_retain_scan_sums: per block of kRowsBlock ordinals the arena bytes of its kept
+// entries and the number of its dead ordinals, their exclusive scans and totals; 64-bit), one host
+// read of RetCtr -- nothing of the dictionary has been written up to here -- then k_retain_compact
+// (kept entries copied into a fresh arena, balanced by bytes like k_rows_copy; ent_off rewritten;
+// dead ordinals marked ent_len -1 / ent_tag 0 and listed ascending as the free list), the table
+// rebuilt by k_slots_clear + k_dict_rehash, and k_retain_side for the surviving host-resolved rows.
+struct RetCtr {
+    unsigned long long bad;        // listed ids that name no live entry
+    unsigned long long bad_first;  // lowest (set << 32 | index) of such an id (~0: none)
+    unsigned long long bytes;      // arena bytes of the kept entries
+    unsigned long long dead;       // ordinals below `issued` that are not kept
+};
+
+// An id is good if it is not negative, its ordinal was issued and is not retired, and the id its
+// arena entry stores is this id (a stale id whose ordinal was reused under another key group is
+// not). Racing writers of a mark byte all store 1; bad ids take one atomic pair per wave.
+__global__ __launch_bounds__(kDictThreads) void k_retain_mark(DictDev d, int64_t issued, int64_t n, const int64_t* ids,
+                                                              int32_t set, uint8_t* mark, RetCtr* rc) {
+    const int64_t i = (int64_t)blockIdx.x * kDictThreads + threadIdx.x;
+    const bool valid = i < n;
+    const int64_t id = valid ? ids[i] : 0;
+    const uint64_t ord = (uint64_t)id >> d.kg_bits;
+    bool ok = valid && id >= 0 && (int64_t)ord < issued;
+    if (ok) ok = d.ent_len[ord] >= 0;
+    if (ok) ok = *reinterpret_cast<const int64_t*>(d.arena + d.ent_off[ord] - 8) == id;
+    if (ok) mark[ord] = 1;
+    const unsigned long long badm = __ballot(valid && !ok);
+    if (badm && (threadIdx.x & 63) == 0) {
+        atomicAdd(&rc->bad, (unsigned long long)__popcll(badm));
+        atomicMin(&rc->bad_first, (unsigned long long)set << 32 | (unsigned long long)(i + __ffsll((long long)badm) - 1));
+    }
+}
+
+// per block of ordinals: sums[b] = arena bytes of its kept entries, sums[nb + b] = its dead ordinals
+__global__ __launch_bounds__(kDictThreads) void k_retain_sums(DictDev d, int64_t issued, const uint8_t* mark, uint64_t* sums,
+                                                              int64_t nb) {
+    __shared__ uint64_t s_wave[kDictThreads / 64];
+    const int64_t o = (int64_t)blockIdx.x * kRowsBlock + threadIdx.x;
+    const bool in = o < issued, keep = in && mark[o];
+    uint64_t bytes, dead;
+    (void)block_exclusive_scan_u64(keep ? entry_bytes(d.ent_len[o]) : 0ull, s_wave, &bytes);
+    (void)block_exclusive_scan_u64(in && !keep ? 1ull : 0ull, s_wave, &dead);
+    if (threadIdx.x == 0) {
+        sums[blockIdx.x] = bytes;
+        sums[nb + blockIdx.x] = dead;
+    }
+}
+
+// one workgroup: both halves of sums -> their exclusive scans, the totals to rc
+__global__ __launch_bounds__(kDictThreads) void k_retain_scan_sums(uint64_t* sums, int64_t nb, RetCtr* rc) {
+    __shared__ uint64_t s_wave[kDictThreads / 64];
+    for (int h = 0; h < 2; h++) {
+        uint64_t* v = sums + h * nb;
+        uint64_t carry = 0;   // (the same in every thread)
+        for (int64_t b0 = 0; b0 < nb; b0 += kDictThreads) {
+            const int64_t b = b0 + threadIdx.x;
+            uint64_t total;
+            const uint64_t ex = block_exclusive_scan_u64(b < nb ? v[b] : 0ull, s_wave, &total);
+            if (b < nb) v[b] = carry + ex;
+            carry += total;
+        }
+        if (threadIdx.x == 0) (h ? rc->dead : rc->bytes) = carry;
+    }
+}
+
+// A workgroup owns kRowsBlock consecutive ordinals. Its kept entries [id][row, padded to 8] land
+// back to back at sums[block] in the new arena, so its output span is contiguous and its threads
+// stride over the span's 8-byte words (k_rows_copy's balance: one very long row does not serialize
+// its neighbours' lanes). Each thread first reads its own ordinal's old entry into LDS, then --
+// no other workgroup reads that ordinal -- rewrites it: ent_off into the new arena, or ent_off -1,
+// ent_len -1, ent_tag 0 and a place in the free list for a dead one.
+__global__ __launch_bounds__(kDictThreads) void k_retain_compact(DictDev d, int64_t issued, const uint8_t* mark,
+                                                                 const uint64_t* sums, int64_t nb, uint64_t* narena,
+                                                                 int64_t* free_out) {
+    __shared__ uint64_t s_wave[kDictThreads / 64];
+    __shared__ int64_t s_off[kRowsBlock + 1];
+    __shared__ int64_t s_src[kRowsBlock];
+    const int64_t o = (int64_t)blockIdx.x * kRowsBlock + threadIdx.x;
+    const bool in = o < issued, keep = in && mark[o];
+    uint64_t bytes, dead;
+    const uint64_t at = sums[blockIdx.x] + block_exclusive_scan_u64(keep ? entry_bytes(d.ent_len[o]) : 0ull, s_wave, &bytes);
+    const uint64_t fp = sums[nb + blockIdx.x] + block_exclusive_scan_u64(in && !keep ? 1ull : 0ull, s_wave, &dead);
+    s_off[threadIdx.x] = (int64_t)at;
+    s_src[threadIdx.x] = keep ? d.ent_off[o] - 8 : -1;
+    if (threadIdx.x == 0) s_off[kRowsBlock] = (int64_t)(sums[blockIdx.x] + bytes);
+    __syncthreads();
+    if (keep) {
+        d.ent_off[o] = (int64_t)at + 8;
+    } else if (in) {
+        d.ent_off[o] = -1;
+        d.ent_len[o] = -1;
+        d.ent_tag[o] = 0;
+        free_out[fp] = o;
+    }
+    const int64_t w1 = s_off[kRowsBlock] >> 3;
+    for (int64_t w = (s_off[0] >> 3) + threadIdx.x; w < w1; w += kDictThreads) {
+        const int64_t b = w << 3;
+        int lo = 0, hi = kRowsBlock;   // s_off[lo] <= b < s_off[hi]; entries of no bytes are never picked
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (s_off[mid] <= b) lo = mid; else hi = mid;
+        }
+        narena[w] = *reinterpret_cast<const uint64_t*>(d.arena + s_src[lo] + (b - s_off[lo]));
+    }
+}
+
+// Surviving host-resolved rows (ent_tag 0: outside the table, found only through the slot of the
+// row that held their tag) after the table was rebuilt: each is tagged again from its arena bytes
+// and takes the slot of its tag if no live row holds it -- one wins per tag, the rest stay with
+// the host. state: 0 retired, 1 still resolved on the host, 2 now in the table.
+__global__ __launch_bounds__(kDictThreads) void k_retain_side(DictDev d, int tag_bits, int64_t n, const int64_t* ords,
+                                                              int32_t* state) {
+    const int64_t i = (int64_t)blockIdx.x * kDictThreads + threadIdx.x;
+    if (i >= n) return;
+    const int64_t o = ords[i];
+    const int32_t len = d.ent_len[o];
+    if (len < 0) {
+        state[i] = 0;
+        return;
+    }
+    const uint8_t* e = d.arena + d.ent_off[o] - 8;
+    const uint32_t* w = reinterpret_cast<const uint32_t*>(e + 8);
+    uint64_t t;
+    int32_t fh;
+    row_hashes(w, len, tag_bits, &t, &fh);
+    uint64_t s = fmix64(t) & d.mask;
+    for (;;) {
+        const unsigned long long old = atomicCAS(&d.slots[s].tag, 0ull, (unsigned long long)t);
+        if (old == 0) break;
+        if (old == t) {
+            state[i] = 1;
+            return;
+        }
+        s = (s + 1) & d.mask;
+    }
+    Slot& sl = d.slots[s];
+    sl.id = *reinterpret_cast<const long long*>(e);
+    for (int k = 0; k < kSlotWords; k++) sl.row[k] = k < (len >> 2) ? w[k] : 0u;
+    sl.loc = loc_of((uint64_t)(d.ent_off[o] - 8), len);
+    d.ent_tag[o] = t;
+    state[i] = 2;
+}
+
 inline unsigned grid_of(int64_t n) { return (unsigned)((n + kDictThreads - 1) / kDictThreads); }
 
 struct Buf {
@@ -709,9 +867,14 @@ struct fg_key_dict {
     int tag_bits = 64;
     hipStream_t stream = nullptr;
     uint64_t cap = 0;   // table slots (power of two)
-    int64_t nids = 0;   // ids handed out (host mirror of counters[0])
+    uint64_t cap0 = 0;  // ... at open: a retain never shrinks the table below it
+    int64_t nids = 0;   // ordinals issued (host mirror of counters[0]): every valid ordinal is below it
     int64_t arena_used = 0;
-    Buf slots, slot_row, ent_off, ent_len, ent_tag, arena, counters;
+    // ordinals a retain retired, ascending (free_ord[nfree]); free_taken of them are in use again
+    // (host mirror of counters[7], capped at nfree). The live entries are live().
+    int64_t nfree = 0, free_taken = 0, retired_total = 0;
+    Buf slots, slot_row, ent_off, ent_len, ent_tag, arena, counters, free_ord;
+    Buf ret_mark, ret_ctr, ret_side;   // fg_key_dict_retain: mark bytes, RetCtr, the side rows' ordinals and states
     Buf in_bytes, in_off, in_len, row_tag, row_kg, row_slot, row_pkg, row_id, miss;   // per-call scratch
     // fg_key_dict_rows: its counters (RowsCtr), the block sums, and for FG_HOST callers the device
     // ids, lengths, offsets and packed bytes; grown on demand and reused across calls
@@ -724,8 +887,10 @@ struct fg_key_dict {
     // assign + verify, and around the two kernel stages of fg_key_dict_rows (ev[3..6]), on the
     // dictionary's stream; summed into the three classes below
     bool timing = false;
-    hipEvent_t ev[7] = {};
-    fg_kernel_stat kstat[3] = {};
+    // ([7..10]: the two kernel stages of fg_key_dict_retain, "dict_retain"; [11..12]: a table rebuild --
+    // k_slots_clear + k_dict_rehash, when the table grows and inside a retain -- "dict_rebuild")
+    hipEvent_t ev[13] = {};
+    fg_kernel_stat kstat[5] = {};
     // fg_key_dict_intern_async: the lookup launched, the rest of the call taken by _wait
     struct Pending {
         bool active = false, host = false;
@@ -745,6 +910,24 @@ struct fg_key_dict {
         err = m;
         return rc;
     }
+    int64_t live() const { return nids - (nfree - free_taken); }
+    // one table rebuild bracketed by ev[11], ev[12] (complete): records = the ordinals rehashed, rows = the slots
+    hipError_t rebuilt() {
+        float ms = 0.f;
+        const hipError_t e = hipEventElapsedTime(&ms, ev[11], ev[12]);
+        kstat[4].launches++;
+        kstat[4].total_ms += ms;
+        kstat[4].records += nids;
+        kstat[4].rows += (int64_t)cap;
+        return e;
+    }
+    // the counters as intern_finish read them: ordinals issued, arena bytes, free ordinals taken
+    void mirror(const unsigned long long* cnt) {
+        nids = (int64_t)cnt[0];
+        arena_used = (int64_t)cnt[1];
+        if (nfree) free_taken = std::min<int64_t>((int64_t)cnt[7], nfree);
+        if (free_taken == nfree) nfree = free_taken = 0;   // spent: k_dict_assign leaves counters[7] alone again
+    }
     DictDev dev() const {
         DictDev d;
         d.slots = slots.as<Slot>();
@@ -754,6 +937,8 @@ struct fg_key_dict {
         d.ent_tag = ent_tag.as<uint64_t>();
         d.arena = arena.as<uint8_t>();
         d.counters = counters.as<unsigned long long>();
+        d.free_ord = free_ord.as<int64_t>();
+        d.nfree = (uint64_t)nfree;
         d.mask = cap - 1;
         d.kg_bits = dict_kg_bits(max_p);
         return d;
@@ -774,6 +959,7 @@ int rebuild(fg_key_dict* d, uint64_t ncap) {
     Buf nslots, nrow;
     DCHK(d, nslots.ensure(sizeof(Slot) * ncap, s));
     DCHK(d, nrow.ensure(4 * ncap, s));
+    if (d->timing) DCHK(d, hipEventRecord(d->ev[11], s));
     hipLaunchKernelGGL(k_slots_clear, dim3(grid_of((int64_t)ncap)), dim3(kDictThreads), 0, s, nslots.as<Slot>(),
                        (int64_t)ncap);
     DCHK(d, hipGetLastError());
@@ -784,8 +970,10 @@ int rebuild(fg_key_dict* d, uint64_t ncap) {
     d->cap = ncap;
     if (d->nids)
         hipLaunchKernelGGL(k_dict_rehash, dim3(grid_of(d->nids)), dim3(kDictThreads), 0, s, d->dev(), d->nids);
+    if (d->timing) DCHK(d, hipEventRecord(d->ev[12], s));
     DCHK(d, hipGetLastError());
     DCHK(d, hipStreamSynchronize(s));
+    if (d->timing) DCHK(d, d->rebuilt());
     return FG_OK;
 }
 
@@ -909,6 +1097,7 @@ int fg_key_dict_open(int32_t device_id, int32_t max_parallelism, int64_t expecte
     if (d->counters.ensure(64, d->stream) != hipSuccess) return FG_EDEVICE;
     if (hipMemsetAsync(d->counters.p, 0, 64, d->stream) != hipSuccess) return FG_EDEVICE;
     if (rebuild(d.get(), pow2_at_least(FG_DICT_INIT * (uint64_t)std::max<int64_t>(expected_keys, 1)))) return FG_EDEVICE;
+    d->cap0 = d->cap;
     *out = d.release();
     return FG_OK;
 }
@@ -1018,7 +1207,7 @@ static int intern_finish(fg_key_dict* d) {
     RowsIn in = pc.in;
     int64_t* ids = pc.ids;
     unsigned long long* ctr = d->counters.as<unsigned long long>();
-    unsigned long long cnt[7];
+    unsigned long long cnt[8];
     DCHK(d, hipMemcpyAsync(cnt, ctr, sizeof cnt, hipMemcpyDeviceToHost, s));
     DCHK(d, hipStreamSynchronize(s));
     if (n == 0) return FG_OK;
@@ -1044,13 +1233,14 @@ static int intern_finish(fg_key_dict* d) {
         DCHK(d, d->arena.ensure((size_t)d->arena_used + (size_t)need + 16, s, (size_t)d->arena_used));
     }
     // 2) the misses, in chunks the table has room for: it stays at most half full even if every
-    // row of a chunk is new. It grows when that room falls under an eighth of the ids (and 1M
-    // rows): to FG_DICT_GROW x (ids + 1M) slots rounded up -- sized by the distinct keys.
+    // row of a chunk is new. It grows when that room falls under an eighth of the live entries (and
+    // 1M rows): to FG_DICT_GROW x (live + 1M) slots rounded up -- sized by the distinct live keys.
     for (int64_t pos = 0; pos < nmiss;) {
-        const int64_t room = (int64_t)(d->cap / 2) - d->nids;
-        if (room < std::max<int64_t>(1 << 20, d->nids / 8))
-            if (int rc = rebuild(d, pow2_at_least(FG_DICT_GROW * (uint64_t)(d->nids + (1 << 20))))) return rc;
-        const int64_t m = std::min<int64_t>(nmiss - pos, (int64_t)(d->cap / 2) - d->nids);
+        const int64_t live = d->live();
+        const int64_t room = (int64_t)(d->cap / 2) - live;
+        if (room < std::max<int64_t>(1 << 20, live / 8))
+            if (int rc = rebuild(d, pow2_at_least(FG_DICT_GROW * (uint64_t)(live + (1 << 20))))) return rc;
+        const int64_t m = std::min<int64_t>(nmiss - pos, (int64_t)(d->cap / 2) - live);
         DCHK(d, d->row_tag.ensure(4 * (size_t)m, s));   // the pending list
         DCHK(d, d->row_slot.ensure(8 * (size_t)m, s));
         DCHK(d, d->row_pkg.ensure(4 * (size_t)m, s));
@@ -1077,8 +1267,7 @@ static int intern_finish(fg_key_dict* d) {
             d->kstat[1].total_ms += ms;
             d->kstat[1].records += m;
         }
-        d->nids = (int64_t)cnt[0];
-        d->arena_used = (int64_t)cnt[1];
+        d->mirror(cnt);
         pos += m;
     }
     collisions = cnt[2];
@@ -1230,6 +1419,157 @@ int fg_key_dict_rows(fg_key_dict* d, int32_t location, int64_t n, const int64_t*
     return FG_OK;
 }
 
+int fg_key_dict_get_stats(fg_key_dict* d, fg_key_dict_stats* out) {
+    if (!d || !out) return FG_EINVAL;
+    out->live = d->live();
+    out->issued = d->nids;
+    out->free_ordinals = d->nfree - d->free_taken;
+    out->arena_bytes = d->arena_used;
+    out->table_slots = (int64_t)d->cap;
+    out->side_rows = (int64_t)d->side.size();
+    out->retired_total = d->retired_total;
+    out->reserved0 = 0;
+    return FG_OK;
+}
+
+int fg_key_dict_retain(fg_key_dict* d, int32_t location, int32_t n_sets, const int64_t* const* ids, const int64_t* counts,
+                       fg_key_dict_stats* out) {
+    if (!d) return FG_EINVAL;
+    if (location != FG_HOST && location != FG_DEVICE) return d->fail(FG_EINVAL, "fg_key_dict_retain: unknown location");
+    if (n_sets < 0 || n_sets > 16 || (n_sets > 0 && (!ids || !counts)))
+        return d->fail(FG_EINVAL, "fg_key_dict_retain: 0..16 sets of ids expected");
+    int64_t n = 0;
+    for (int k = 0; k < n_sets; k++) {
+        if (counts[k] < 0 || counts[k] > 0x7fffffff || (counts[k] > 0 && !ids[k]))
+            return d->fail(FG_EINVAL,
+                           "fg_key_dict_retain: set " + std::to_string(k) + ": a count in [0, 2^31) and its ids expected");
+        n += counts[k];
+    }
+    if (d->pend.active) return d->fail(FG_ESTATE, "fg_key_dict_retain: an async intern is pending (fg_key_dict_intern_wait)");
+    if (hipSetDevice(d->device) != hipSuccess) return d->fail(FG_EDEVICE, "hipSetDevice failed");
+    hipStream_t s = d->stream;
+    const bool host = location == FG_HOST;
+    const int64_t issued = d->nids;
+    const int64_t nb = (issued + kRowsBlock - 1) / kRowsBlock;
+    // 1) mark and plan: scratch only -- the dictionary is read, not written
+    DCHK(d, d->ret_mark.ensure((size_t)std::max<int64_t>(issued, 1), s));
+    DCHK(d, d->ret_ctr.ensure(sizeof(RetCtr), s));
+    DCHK(d, d->rows_sums.ensure(16 * (size_t)std::max<int64_t>(nb, 1), s));
+    if (host && n) DCHK(d, d->rows_ids.ensure(8 * (size_t)n, s));
+    uint8_t* mark = d->ret_mark.as<uint8_t>();
+    RetCtr* rc = d->ret_ctr.as<RetCtr>();
+    uint64_t* sums = d->rows_sums.as<uint64_t>();
+    DCHK(d, hipMemsetAsync(mark, 0, (size_t)std::max<int64_t>(issued, 1), s));
+    DCHK(d, hipMemsetAsync(rc, 0, sizeof(RetCtr), s));
+    DCHK(d, hipMemsetAsync(&rc->bad_first, 0xff, 8, s));
+    if (d->timing) DCHK(d, hipEventRecord(d->ev[7], s));
+    int64_t at = 0;
+    for (int k = 0; k < n_sets; k++) {
+        if (!counts[k]) continue;
+        const int64_t* di = ids[k];
+        if (host) {
+            DCHK(d, hipMemcpyAsync(d->rows_ids.as<int64_t>() + at, ids[k], 8 * (size_t)counts[k], hipMemcpyHostToDevice, s));
+            di = d->rows_ids.as<int64_t>() + at;
+            at += counts[k];
+        }
+        hipLaunchKernelGGL(k_retain_mark, dim3(grid_of(counts[k])), dim3(kDictThreads), 0, s, d->dev(), issued, counts[k], di,
+                           (int32_t)k, mark, rc);
+    }
+    if (nb) {
+        hipLaunchKernelGGL(k_retain_sums, dim3((unsigned)nb), dim3(kDictThreads), 0, s, d->dev(), issued, (const uint8_t*)mark,
+                           sums, nb);
+        hipLaunchKernelGGL(k_retain_scan_sums, dim3(1), dim3(kDictThreads), 0, s, sums, nb, rc);
+    }
+    if (d->timing) DCHK(d, hipEventRecord(d->ev[8], s));
+    DCHK(d, hipGetLastError());
+    RetCtr hc;   // the one host read: bad ids, the new arena's size, the dead ordinals
+    DCHK(d, hipMemcpyAsync(&hc, rc, sizeof hc, hipMemcpyDeviceToHost, s));
+    DCHK(d, hipStreamSynchronize(s));
+    float ms = 0.f;
+    if (d->timing) DCHK(d, hipEventElapsedTime(&ms, d->ev[7], d->ev[8]));
+    auto timed = [&](float t, int64_t kept) {
+        if (!d->timing) return;
+        d->kstat[3].launches++;
+        d->kstat[3].total_ms += t;
+        d->kstat[3].records += issued;
+        d->kstat[3].rows += kept;
+    };
+    if (hc.bad) {
+        timed(ms, 0);
+        return d->fail(FG_EINVAL, "fg_key_dict_retain: " + std::to_string(hc.bad) +
+                                      " ids name no live entry (negative, never issued, retired, or stale); the first at set " +
+                                      std::to_string(hc.bad_first >> 32) + " index " +
+                                      std::to_string(hc.bad_first & 0xffffffffull) + "; the dictionary is unchanged");
+    }
+    const int64_t dead = (int64_t)hc.dead, kept = issued - dead;
+    const int64_t before = d->live();
+    // 2) everything the new state needs is allocated before anything is modified
+    const uint64_t ncap =
+        std::min<uint64_t>(d->cap, std::max<uint64_t>(d->cap0, pow2_at_least(FG_DICT_GROW * (uint64_t)(kept + (1 << 20)))));
+    std::vector<int64_t> side_ord;
+    std::vector<std::unordered_map<std::string, int64_t>::iterator> side_it;
+    for (auto it = d->side.begin(); it != d->side.end(); ++it) {
+        side_ord.push_back((int64_t)((uint64_t)it->second >> dict_kg_bits(d->max_p)));
+        side_it.push_back(it);
+    }
+    const int64_t nside = (int64_t)side_ord.size();
+    Buf narena, nslots, nrow, nfree;
+    DCHK(d, narena.ensure((size_t)hc.bytes + 16, s));
+    DCHK(d, nslots.ensure(sizeof(Slot) * ncap, s));
+    DCHK(d, nrow.ensure(4 * ncap, s));
+    DCHK(d, nfree.ensure(8 * (size_t)std::max<int64_t>(dead, 1), s));
+    if (nside) DCHK(d, d->ret_side.ensure(12 * (size_t)nside, s));
+    // 3) compact, rebuild, side rows
+    if (d->timing) DCHK(d, hipEventRecord(d->ev[9], s));
+    if (nb)
+        hipLaunchKernelGGL(k_retain_compact, dim3((unsigned)nb), dim3(kDictThreads), 0, s, d->dev(), issued, (const uint8_t*)mark,
+                           (const uint64_t*)sums, nb, narena.as<uint64_t>(), nfree.as<int64_t>());
+    if (d->timing) DCHK(d, hipEventRecord(d->ev[11], s));
+    hipLaunchKernelGGL(k_slots_clear, dim3(grid_of((int64_t)ncap)), dim3(kDictThreads), 0, s, nslots.as<Slot>(), (int64_t)ncap);
+    auto swap = [](Buf& a, Buf& b) {
+        std::swap(a.p, b.p);
+        std::swap(a.bytes, b.bytes);
+    };
+    swap(d->arena, narena);   // (the old ones are freed on return: the stream is idle by then)
+    swap(d->slots, nslots);
+    swap(d->slot_row, nrow);
+    swap(d->free_ord, nfree);
+    d->cap = ncap;
+    d->arena_used = (int64_t)hc.bytes;
+    d->nfree = dead;
+    d->free_taken = 0;
+    d->retired_total += before - kept;
+    if (issued) hipLaunchKernelGGL(k_dict_rehash, dim3(grid_of(issued)), dim3(kDictThreads), 0, s, d->dev(), issued);
+    if (d->timing) DCHK(d, hipEventRecord(d->ev[12], s));
+    int64_t* side_dev = d->ret_side.as<int64_t>();
+    int32_t* state_dev = reinterpret_cast<int32_t*>(side_dev + nside);
+    if (nside) {
+        DCHK(d, hipMemcpyAsync(side_dev, side_ord.data(), 8 * (size_t)nside, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_retain_side, dim3(grid_of(nside)), dim3(kDictThreads), 0, s, d->dev(), d->tag_bits, nside,
+                           (const int64_t*)side_dev, state_dev);
+    }
+    if (d->timing) DCHK(d, hipEventRecord(d->ev[10], s));
+    DCHK(d, hipGetLastError());
+    const unsigned long long c2[2] = {(unsigned long long)issued, hc.bytes}, zero = 0;
+    unsigned long long* ctr = d->counters.as<unsigned long long>();
+    DCHK(d, hipMemcpyAsync(ctr, c2, sizeof c2, hipMemcpyHostToDevice, s));
+    DCHK(d, hipMemcpyAsync(ctr + 7, &zero, 8, hipMemcpyHostToDevice, s));
+    std::vector<int32_t> state((size_t)nside);
+    if (nside) DCHK(d, hipMemcpyAsync(state.data(), state_dev, 4 * (size_t)nside, hipMemcpyDeviceToHost, s));
+    DCHK(d, hipStreamSynchronize(s));
+    for (int64_t i = 0; i < nside; i++)   // retired side rows leave the map, and those the table holds now
+        if (state[i] != 1) d->side.erase(side_it[i]);
+    if (d->timing) {
+        float ms2 = 0.f;
+        DCHK(d, hipEventElapsedTime(&ms2, d->ev[9], d->ev[10]));
+        ms += ms2;
+        DCHK(d, d->rebuilt());
+    }
+    timed(ms, kept);
+    if (out) return fg_key_dict_get_stats(d, out);
+    return FG_OK;
+}
+
 int fg_partition_keyed_by_owner(fg_key_dict* d, void* stream, int64_t n, int32_t ncols, const int64_t* const* cols,
                                 int32_t parallelism, int64_t* const* out_cols, int64_t* counts, int32_t* out_key_lengths,
                                 uint8_t* out_key_bytes, int64_t cap_bytes, int64_t* out_byte_counts, int64_t* out_nbytes) {
@@ -1268,7 +1608,7 @@ int fg_key_dict_copy_arena(fg_key_dict* d, int64_t begin, int64_t nbytes, uint8_
     return FG_OK;
 }
 
-int64_t fg_key_dict_size(fg_key_dict* d) { return d ? d->nids : -1; }
+int64_t fg_key_dict_size(fg_key_dict* d) { return d ? d->live() : -1; }
 
 void* fg_key_dict_stream(fg_key_dict* d) { return d ? (void*)d->stream : nullptr; }
 
@@ -1280,6 +1620,8 @@ int fg_key_dict_set_timing(fg_key_dict* d, int32_t on) {
         std::snprintf(d->kstat[0].name, sizeof d->kstat[0].name, "dict_probe");
         std::snprintf(d->kstat[1].name, sizeof d->kstat[1].name, "dict_assign");
         std::snprintf(d->kstat[2].name, sizeof d->kstat[2].name, "dict_rows");
+        std::snprintf(d->kstat[3].name, sizeof d->kstat[3].name, "dict_retain");
+        std::snprintf(d->kstat[4].name, sizeof d->kstat[4].name, "dict_rebuild");
     }
     d->timing = on != 0;
     return FG_OK;
@@ -1287,7 +1629,7 @@ int fg_key_dict_set_timing(fg_key_dict* d, int32_t on) {
 
 int fg_key_dict_kernel_stats(fg_key_dict* d, fg_kernel_stat* out, int32_t max, int32_t* count) {
     if (!d || !count || (max > 0 && !out)) return FG_EINVAL;
-    *count = d->ev[0] ? 3 : 0;
+    *count = d->ev[0] ? 5 : 0;
     for (int i = 0; i < *count && i < max; i++) out[i] = d->kstat[i];
     return FG_OK;
 }

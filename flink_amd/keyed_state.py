@@ -91,6 +91,18 @@ def merge_acc(a: tuple, b: tuple, f64: bool) -> tuple:
     return (int(cs), int(cv), int(s), int(mn), int(mx))
 
 
+RETAIN_MIN_LIVE = 1 << 16
+
+
+def retain_due(live: int, state_rows: int, factor: int, min_live: int = RETAIN_MIN_LIVE) -> bool:
+    """Whether a barrier retires the dictionary's dead keys (GpuSlicingWindowProcessor.writeKeyedState,
+    -Dflinkgpu.dictRetainFactor): the dictionary holds `live` keys, the snapshot plan `state_rows`
+    rows of state. Due iff factor > 0, live >= 2^16 and live > factor * state_rows. A due barrier
+    takes a full image (`wanted_slices(..., force_all=True)`), whose key column is every id the
+    operator holds, and passes it to KeyDictionary.retain."""
+    return factor > 0 and live >= min_live and live > factor * state_rows
+
+
 class WindowAggsState:
     """The heap backend's window-aggs ValueState + event-time timers of one subtask (a model, with
     the operation counts a checkpoint costs the task thread)."""
@@ -183,10 +195,14 @@ class WindowAggsState:
             changed[ns] = True
         return contrib, changed, reset
 
-    def wanted_slices(self, plan_slices, progress: int) -> np.ndarray:
+    def wanted_slices(self, plan_slices, progress: int, force_all: bool = False) -> np.ndarray:
         """The mask of fg_snapshot_state_select for a plan (fg_snapshot_plan's slices, `progress`
         its timer watermark): every slice whose namespace write_image would rewrite -- changed, or
-        rebuilt (all contributors of a CUMULATE namespace when one of them changed or fired)."""
+        rebuilt (all contributors of a CUMULATE namespace when one of them changed or fired).
+        `force_all` (a barrier at which retain_due holds) selects every slice: the full image
+        rewrites unchanged namespaces idempotently and its key column lists every id held."""
+        if force_all:
+            return np.ones(len(plan_slices["slice_end"]), dtype=np.uint8)
         _, changed, _ = self._plan(plan_slices, progress)
         return np.array([1 if changed[self.spec.namespace(se, progress)] else 0
                          for se in plan_slices["slice_end"].tolist()], dtype=np.uint8)

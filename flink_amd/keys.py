@@ -7,6 +7,7 @@ TC/data/binary/BinarySection.java:62-73) and the key group is
 murmurHash(hashBytesByWords(row)) % maxParallelism (BinarySection.hashCode :76-78,
 KeyGroupRangeAssignment.java:63-77). `KeyDictionary.intern` maps such rows to 64-bit ids on the
 GPU (equal rows -> equal ids, exact), which the window operators aggregate as BIGINT keys;
+`retain` keeps the ids that still hold state and retires the rest (their ordinals are reused);
 `rows` gathers the packed key rows of ids on the GPU (fired rows, checkpoints; `lookup` is its
 list-of-bytes form) and `reintern` carries ids from one dictionary into another (rescale).
 `key_row` / `decode_key_row` write and read key rows the way BinaryRowWriter does (writer/BinaryRowWriter.java, AbstractBinaryWriter.java:
@@ -290,15 +291,59 @@ class KeyDictionary:
         raw = buf.tobytes()
         return [raw[o:o + n_] for o, n_ in zip(off[:-1].tolist(), ln.tolist())]
 
+    @staticmethod
+    def _stats_dict(st) -> dict:
+        return {f: int(getattr(st, f)) for f, _ in L.FgKeyDictStats._fields_ if f != "reserved0"}
+
+    def stats(self) -> dict:
+        """fg_key_dict_get_stats: live, issued, free_ordinals, arena_bytes, table_slots, side_rows,
+        retired_total."""
+        st = L.FgKeyDictStats()
+        self._check(self._lib.fg_key_dict_get_stats(self._h, C.byref(st)))
+        return self._stats_dict(st)
+
+    def retain(self, *id_arrays) -> dict:
+        """fg_key_dict_retain: keep exactly the ids of the given arrays (numpy arrays, or torch
+        tensors on the device -- one kind per call; up to 16, e.g. the key column of every handle's
+        state image), retire every other entry and reuse its ordinal for later interns. No array
+        empties the dictionary. Returns the stats after the call. After it the caller must hold no
+        id outside the arrays; an id that names no live entry raises (the dictionary unchanged)."""
+        dev = any(hasattr(a, "data_ptr") for a in id_arrays)
+        if dev:
+            import torch
+            if not all(hasattr(a, "data_ptr") for a in id_arrays):
+                raise TypeError("retain: numpy arrays or device tensors, not both")
+            arrs = [a.to(torch.int64).contiguous() for a in id_arrays]
+            for a in arrs:
+                if a.numel():
+                    ext = self.__dict__.get("_ext_stream")
+                    if ext is None or ext.device != a.device:
+                        ext = self._ext_stream = torch.cuda.ExternalStream(self._lib.fg_key_dict_stream(self._h),
+                                                                           device=a.device)
+                    ext.wait_stream(torch.cuda.current_stream(a.device))   # the ids' producer first
+            ptrs = [a.data_ptr() for a in arrs]
+            counts = [a.numel() for a in arrs]
+        else:
+            arrs = [np.ascontiguousarray(a, dtype=np.int64).reshape(-1) for a in id_arrays]
+            ptrs = [a.ctypes.data for a in arrs]
+            counts = [a.size for a in arrs]
+        k = len(arrs)
+        pa = (C.c_void_p * max(k, 1))(*ptrs)
+        ca = (C.c_int64 * max(k, 1))(*counts)
+        st = L.FgKeyDictStats()
+        self._check(self._lib.fg_key_dict_retain(self._h, L.DEVICE if dev else L.HOST, k, pa, ca, C.byref(st)))
+        return self._stats_dict(st)
+
     def set_timing(self, on: bool = True):
         """HIP-event timing of the dictionary's kernels (kernel_stats)."""
         self._check(self._lib.fg_key_dict_set_timing(self._h, 1 if on else 0))
 
     def kernel_stats(self) -> dict:
-        """{"dict_probe" | "dict_assign" | "dict_rows": dict(launches, total_ms, records, rows)}."""
-        arr = (L.FgKernelStat * 4)()
+        """{"dict_probe" | "dict_assign" | "dict_rows" | "dict_retain" | "dict_rebuild": dict(launches,
+        total_ms, records, rows)}."""
+        arr = (L.FgKernelStat * 8)()
         n = C.c_int32()
-        self._check(self._lib.fg_key_dict_kernel_stats(self._h, arr, 4, C.byref(n)))
+        self._check(self._lib.fg_key_dict_kernel_stats(self._h, arr, 8, C.byref(n)))
         return {arr[i].name.decode(): dict(launches=arr[i].launches, total_ms=arr[i].total_ms,
                                            records=arr[i].records, rows=arr[i].rows) for i in range(n.value)}
 

@@ -695,8 +695,9 @@ void fg_comm_close(fg_comm* c);
  * 2^31 for 16.7M keys at max parallelism 128, so the window engine stages them as 32-bit keys). The ids are the BIGINT key
  * column of fg_add_batch / the key field of fg_add_rows; FG_KEYHASH_DICT_ID routes them by the
  * carried key group; fired rows' ids map back to their rows with fg_key_dict_rows. A handle is
- * single-threaded like fg_handle; ids are stable for the dictionary's life (a restored operator
- * re-interns the key rows of its state image first). */
+ * single-threaded like fg_handle; an id is stable until fg_key_dict_retain retires it -- for the
+ * dictionary's life if that is never called (a restored operator re-interns the key rows of its
+ * state image first). */
 typedef struct fg_key_dict fg_key_dict;
 int  fg_key_dict_open(int32_t device_id, int32_t max_parallelism, int64_t expected_keys, fg_key_dict** out);
 /* n key rows: row i = bytes[offsets[i], offsets[i] + lengths[i]) (nbytes = the buffer's size),
@@ -802,14 +803,65 @@ int  fg_partition_keyed_by_owner(fg_key_dict* d, void* stream, int64_t n, int32_
  * global_keys only inside _end (the one-call forms use both), so the lock under which the caller
  * makes those calls (its operator lock) must also cover its own use of the two dictionaries. */
 int  fg_comm_set_key_dicts(fg_comm* c, fg_key_dict* local_keys, fg_key_dict* global_keys);
-/* The arena (device memory, rows padded to 8 bytes) and its used size; valid until the next intern. */
+/* Retire keys without state and reuse their ids (ABI 16, added). The reference clears the keyed
+ * state of a (key, window) when the window expires; a dictionary that only grows keeps a slot, an
+ * arena entry and an ordinal for every key ever seen. fg_key_dict_retain keeps exactly the listed
+ * ids (the key column of a state image), retires every other entry, compacts the arena, rebuilds the
+ * table and hands the retired ordinals out again; fg_key_dict_get_stats reports the sizes. A
+ * dictionary that never calls retain behaves as before.
+ *   ids[0 .. n_sets) and counts are host arrays (n_sets 0..16: one image per handle or slice, no
+ *   concatenation); the arrays ids[k] point to hold counts[k] ids each (0 .. 2^31 - 1) and are all
+ *   FG_HOST or all FG_DEVICE (location); device arrays are read on the dictionary's stream under the
+ *   ordering rule of fg_key_dict_intern. Duplicates are allowed. The call is synchronous: everything
+ *   below is complete when it returns. `out` (optional) receives the stats after the call.
+ * Every listed id is validated before anything changes: it is invalid if it is negative, its ordinal
+ * is >= issued, its entry is retired, or the id stored in its arena entry differs (a stale id whose
+ * ordinal was reused under another key group). Returns
+ *   FG_EINVAL  a NULL d, an unknown location, n_sets outside 0..16, a NULL ids / counts with
+ *              n_sets > 0, a count outside [0, 2^31), a NULL set with a count > 0; or, after one
+ *              host read of the call's counters (as fg_key_dict_rows), an invalid id -- the message
+ *              gives how many and the lowest (set, index); the dictionary is unchanged;
+ *   FG_ESTATE  while an async intern is pending; the dictionary is unchanged;
+ *   FG_EDEVICE a device error; the new arena, table and free list are allocated before anything is
+ *              modified, so a failed allocation leaves the dictionary unchanged.
+ * Kept ids keep their id and their row: fg_key_dict_rows, fg_key_dict_lookup, fg_key_dict_intern of
+ * the row and fg_partition_keyed_by_owner answer as before. Every other entry is retired: its row is
+ * no longer in the table (a later intern of the same bytes is a new key), its arena bytes are gone,
+ * fg_key_dict_rows and fg_partition_keyed_by_owner report its id as unknown (as an id past the size)
+ * and fg_key_dict_lookup gives -1 / -1 -- until its ordinal is reused, after which the id may be
+ * another key's. The contract: after retain the caller holds no id outside the live sets.
+ * n_sets == 0, or all counts 0, is legal and empties the dictionary. Later interns take the lowest
+ * free ordinals first and fresh ones only when none is free, so `issued` is the largest number of
+ * keys ever alive at once (up to rows resolved on the host after a tag collision, which take fresh
+ * ordinals), not the number ever seen -- ids stay below 2^31 on a bounded live set. After the call
+ * arena_bytes is exactly the sum of 8 + ((len + 7) & ~7) over the live rows, and the table has
+ * min(current, max(slots at open, pow2 >= FG_DICT_GROW x (live + 2^20))) slots. */
+typedef struct fg_key_dict_stats {
+    int64_t live;            /* = fg_key_dict_size */
+    int64_t issued;          /* ordinals ever handed out: every id is below issued << kg_bits */
+    int64_t free_ordinals;   /* retired ordinals not yet reused */
+    int64_t arena_bytes;     /* arena bytes in use */
+    int64_t table_slots;
+    int64_t side_rows;       /* rows resolved on the host (tag collisions) */
+    int64_t retired_total;   /* entries retired by all retain calls */
+    int64_t reserved0;
+} fg_key_dict_stats;
+int  fg_key_dict_get_stats(fg_key_dict* d, fg_key_dict_stats* out);
+int  fg_key_dict_retain(fg_key_dict* d, int32_t location, int32_t n_sets,
+                        const int64_t* const* ids, const int64_t* counts,
+                        fg_key_dict_stats* out /* optional */);
+/* The arena (device memory, rows padded to 8 bytes) and its used size; valid until the next intern
+ * or retain. */
 int  fg_key_dict_arena(fg_key_dict* d, const uint8_t** dev_bytes, int64_t* size);
 int  fg_key_dict_copy_arena(fg_key_dict* d, int64_t begin, int64_t nbytes, uint8_t* host);
-int64_t fg_key_dict_size(fg_key_dict* d);   /* distinct key rows interned */
+int64_t fg_key_dict_size(fg_key_dict* d);   /* distinct key rows interned and not retired (live) */
 void* fg_key_dict_stream(fg_key_dict* d);   /* the dictionary's device stream (hipStream_t) */
 /* HIP-event timing of the dictionary's kernels (per chunk: "dict_probe", then "dict_assign" =
  * assign + verify of the rows new in the chunk; per fg_key_dict_rows call: "dict_rows" = all of
- * the call's kernels, records = its ids); fg_key_dict_kernel_stats copies them. */
+ * the call's kernels, records = its ids; per fg_key_dict_retain call: "dict_retain" = all of the
+ * call's kernels, records = the ordinals issued, rows = the entries kept; per table rebuild, when
+ * the table grows and inside every retain: "dict_rebuild" = the clear and the rehash, records = the
+ * ordinals, rows = the slots); fg_key_dict_kernel_stats copies them. */
 int  fg_key_dict_set_timing(fg_key_dict* d, int32_t on);
 int  fg_key_dict_kernel_stats(fg_key_dict* d, fg_kernel_stat* out, int32_t max, int32_t* count);
 const char* fg_key_dict_last_error(fg_key_dict* d);

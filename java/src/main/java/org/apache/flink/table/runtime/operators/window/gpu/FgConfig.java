@@ -63,6 +63,20 @@ public final class FgConfig {
      */
     public static boolean firedRuns = Boolean.getBoolean("flinkgpu.firedRuns");
 
+    /**
+     * When a checkpoint retires the keys of the dictionary that hold no state (fg_key_dict_retain;
+     * STRING / multi-column / NULL keys only): at a barrier where the dictionary's live keys are at
+     * least 2^16 and more than dictRetainFactor x the rows of state the snapshot plan lists. Such a
+     * barrier writes a full image and keeps exactly its keys. 0 (the default) never retires:
+     * -Dflinkgpu.dictRetainFactor=4 bounds the dictionary by 4 x the state.
+     */
+    public static long dictRetainFactor = Long.getLong("flinkgpu.dictRetainFactor", 0);
+
+    /** flink_amd/keyed_state.py retain_due */
+    public static boolean retainDue(long live, long stateRows, long factor) {
+        return factor > 0 && live >= (1L << 16) && live > factor * stateRows;
+    }
+
     private FgConfig() {}
 
     /** The image of spec for the subtask owning key groups [kgStart, kgEnd]. */

@@ -251,6 +251,17 @@ public final class FlinkGpu {
             ByteBuffer outOffsets,
             ByteBuffer outLengths);
 
+    /**
+     * fg_key_dict_retain (one FG_HOST set): keep exactly ids[0 .. n), retire every other entry and
+     * reuse its ordinal for later interns; n == 0 empties the dictionary. Returns the 8 words of
+     * fg_key_dict_stats after the call: [live, issued, freeOrdinals, arenaBytes, tableSlots,
+     * sideRows, retiredTotal, 0]. After it the caller must hold no id outside ids.
+     */
+    public static native long[] dictRetain(long d, ByteBuffer ids, int n);
+
+    /** fg_key_dict_get_stats: the 8 words as dictRetain returns them. */
+    public static native long[] dictStats(long d);
+
     /** fg_key_dict_copy_arena. */
     public static native void dictCopyArena(long d, long begin, long nbytes, ByteBuffer out);
 

@@ -226,6 +226,23 @@ final class GpuKeyRows implements AutoCloseable {
         FlinkGpu.dictIntern(dict, all, at, off, len, keyRows.length, keys, null);
     }
 
+    /** the dictionary's live keys (fg_key_dict_stats.live); 0 for a BIGINT key */
+    long liveKeys() {
+        return bigint ? 0 : FlinkGpu.dictStats(dict)[0];
+    }
+
+    /**
+     * keep exactly the ids keys[0 .. count) -- the key column of a full state image, every id the
+     * operator holds -- and retire every other key of the dictionary (one dictRetain); a no-op for
+     * a BIGINT key. Ids outside keys must not be used afterwards.
+     */
+    void retain(ByteBuffer keys, int count) {
+        if (bigint) {
+            return;
+        }
+        FlinkGpu.dictRetain(dict, keys, count);
+    }
+
     @Override
     public void close() {
         if (dict != 0) {

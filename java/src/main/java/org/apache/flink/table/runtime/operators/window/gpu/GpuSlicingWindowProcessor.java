@@ -387,6 +387,12 @@ public final class GpuSlicingWindowProcessor implements SlicingWindowProcessor<L
      * their namespaces: an unselected slice is unchanged, so the backend holds its keys.
      * Mirror: flink_amd/keyed_state.py wanted_slices / write_delta (tests/test_gpu_snapshot_select.py
      * checks it against the full rewrite, and a failover restored from the written backend).
+     *
+     * <p>Keys of any type: the dictionary keeps every key ever interned until it is told which still
+     * matter. With -Dflinkgpu.dictRetainFactor=F a barrier at which the dictionary's live keys exceed
+     * F x the plan's rows of state (and 2^16) selects every slice and, once the rows are written,
+     * calls keys.retain on the image's key column (keyed_state.retain_due, wanted_slices(force_all);
+     * tests/test_gpu_key_retire.py).
      */
     private void writeKeyedState() throws Exception {
         KeyedStateBackend<RowData> backend = ctx.getKeyedStateBackend();
@@ -412,11 +418,21 @@ public final class GpuSlicingWindowProcessor implements SlicingWindowProcessor<L
                 changed.put(e.getKey(), true);
             }
         }
+        // a barrier at which the dictionary holds many more keys than the state (FgConfig.dictRetainFactor)
+        // takes a full image -- unchanged namespaces are rewritten idempotently -- whose key column is
+        // every id the operator holds: the batch is flushed and the held rows are collected
+        long stateRows = 0;
+        for (int i = 0; i < ns; i++) {
+            stateRows += plan[1 + 2 * ns + i];
+        }
+        final boolean retain =
+                FgConfig.dictRetainFactor > 0
+                        && FgConfig.retainDue(keys.liveKeys(), stateRows, FgConfig.dictRetainFactor);
         // the mask: every slice of a namespace to rewrite; nothing may touch the handle between the
         // plan and the select
         long[] want = new long[ns];
         for (int i = 0; i < ns; i++) {
-            want[i] = changed.get(nsOf[i]) ? 1 : 0;
+            want[i] = retain || changed.get(nsOf[i]) ? 1 : 0;
         }
         // the selected slices' export and host copy run on the GPU while the previous image is cleared
         FlinkGpu.snapshotSelectAsync(handle, want);
@@ -503,6 +519,9 @@ public final class GpuSlicingWindowProcessor implements SlicingWindowProcessor<L
         }
         imageContrib = contrib;
         lastNextEnd = nextEnd;
+        if (retain) {   // every other key of the dictionary holds no state: retired, its id reused
+            keys.retain(cols[0], (int) stateRows);
+        }
     }
 
     /** the namespace of a slice's state at `progress` (CUMULATE: a fired slice's window's first slice) */

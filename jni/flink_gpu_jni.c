@@ -603,6 +603,38 @@ JNIEXPORT jlong JNICALL FN(dictRows)(JNIEnv* env, jclass cls, jlong dp, jobject 
     return nbytes;
 }
 
+static jlongArray dict_stats_array(JNIEnv* env, const fg_key_dict_stats* st) {
+    const jlong v[8] = {st->live, st->issued, st->free_ordinals, st->arena_bytes, st->table_slots, st->side_rows,
+                        st->retired_total, st->reserved0};
+    jlongArray out = (*env)->NewLongArray(env, 8);
+    if (out) (*env)->SetLongArrayRegion(env, out, 0, 8, v);
+    return out;
+}
+
+/* long[] dictRetain(long d, ByteBuffer ids, int n): fg_key_dict_retain of one host set -- the n ids
+ * are kept, every other entry is retired and its ordinal reused; n == 0 (ids may be null) empties the
+ * dictionary. Returns the 8 words of fg_key_dict_stats after the call: [live, issued, freeOrdinals,
+ * arenaBytes, tableSlots, sideRows, retiredTotal, 0]. */
+JNIEXPORT jlongArray JNICALL FN(dictRetain)(JNIEnv* env, jclass cls, jlong dp, jobject ids, jint n) {
+    (void)cls;
+    fg_key_dict* d = (fg_key_dict*)(intptr_t)dp;
+    const int64_t* i = (const int64_t*)addr(env, ids);
+    if ((*env)->ExceptionCheck(env)) return NULL;
+    const int64_t count = n;
+    fg_key_dict_stats st;
+    if (dcheck(env, d, fg_key_dict_retain(d, FG_HOST, n > 0 ? 1 : 0, &i, &count, &st))) return NULL;
+    return dict_stats_array(env, &st);
+}
+
+/* long[] dictStats(long d): fg_key_dict_get_stats, the 8 words as dictRetain returns them */
+JNIEXPORT jlongArray JNICALL FN(dictStats)(JNIEnv* env, jclass cls, jlong dp) {
+    (void)cls;
+    fg_key_dict* d = (fg_key_dict*)(intptr_t)dp;
+    fg_key_dict_stats st;
+    if (dcheck(env, d, fg_key_dict_get_stats(d, &st))) return NULL;
+    return dict_stats_array(env, &st);
+}
+
 /* void dictCopyArena(long d, long begin, long nbytes, ByteBuffer out) */
 JNIEXPORT void JNICALL FN(dictCopyArena)(JNIEnv* env, jclass cls, jlong dp, jlong begin, jlong nbytes, jobject out) {
     (void)cls;
