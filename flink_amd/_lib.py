@@ -135,6 +135,7 @@ FLAG_PROCTIME = 4
 FLAG_WINDOWED = 8
 FLAG_PURGING_TRIGGER = 16
 BATCH_KEY32, BATCH_ROWTIME32, BATCH_VAL32 = 1, 2, 4   # fg_batch.format
+TOPN_MAX = 1024   # FG_TOPN_MAX
 
 # every symbol include/flinkgpu.h declares
 EXPORTS = (
@@ -146,6 +147,7 @@ EXPORTS = (
     "fg_snapshot_plan", "fg_snapshot_state_select_async", "fg_snapshot_state_select",
     "fg_set_fired_runs", "fg_fired_runs",
     "fg_set_late_output", "fg_collect_late",
+    "fg_set_fired_topn",
     "fg_stream",
     "fg_last_error", "fg_close", "fg_key_groups", "fg_partition_by_owner", "fg_partition_columns_by_owner",
     "fg_abi_version", "fg_key_dict_open", "fg_key_dict_intern", "fg_key_dict_intern_async",
@@ -285,6 +287,9 @@ def load():
         L.fg_set_late_output.argtypes = [P, C.c_int32]
         L.fg_collect_late.argtypes = [P, C.c_int32, C.POINTER(FgLateRecords)]
         L.fg_set_late_output.restype = L.fg_collect_late.restype = C.c_int
+    if hasattr(L, "fg_set_fired_topn"):   # (the same)
+        L.fg_set_fired_topn.argtypes = [P, C.c_int32, C.c_int32, C.c_int32]
+        L.fg_set_fired_topn.restype = C.c_int
     if hasattr(L, "fg_key_dict_retain"):   # (the same)
         L.fg_key_dict_get_stats.argtypes = [P, C.POINTER(FgKeyDictStats)]
         L.fg_key_dict_retain.argtypes = [P, C.c_int32, C.c_int32, C.POINTER(P), C.POINTER(C.c_int64),

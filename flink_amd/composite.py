@@ -50,6 +50,9 @@ class CompositeWindowAggOperator:
     def __init__(self, window, aggs, **kw):
         if kw.get("local_partials"):
             raise ValueError("the local phase emits one partial accumulator: open one operator per kind")
+        if kw.get("topn") is not None:
+            raise ValueError("topn: each handle of a composite operator would select its own rows by its own "
+                             "aggregates, and the row sets would no longer join -- use one WindowAggOperator")
         self.codes, groups = accumulator_groups(aggs)
         self.window = window
         self.ops = []

@@ -175,13 +175,13 @@ constexpr int64_t kHeavyChunk = 1 << 16;
 
 enum KClass { K_COUNT = 0, K_SCAN, K_SCATTER, K_PART1, K_PART2, K_FLUSH, K_FLUSH_FIRE, K_FIRE, K_EXPORT, K_RESTORE,
               K_HEAVY, K_TILE1, K_TILE_FIRE, K_TILE_MAT, K_TILE_FLUSH, K_TILE_SPLIT, K_RR_FILTER, K_RR_SCATTER,
-              K_EXPORT_GROUP, K_EXPORT_SELECT, K_LATE_OUT, K_NCLASS };
+              K_EXPORT_GROUP, K_EXPORT_SELECT, K_LATE_OUT, K_TOPN, K_NCLASS };
 const char* const kClassName[K_NCLASS] = {"ingest_count", "ingest_scan",      "ingest_scatter", "ingest_part1",
                                            "ingest_part2", "merge_flush",      "merge_flush_fire", "merge_fire",
                                            "export",       "restore",          "merge_heavy",      "tile_part1",
                                            "tile_fire",    "tile_materialize", "tile_flush",       "tile_split_fire",
                                            "restore_filter", "restore_scatter", "export_group",   "export_select",
-                                           "late_out"};
+                                           "late_out",       "topn"};
 struct KStat {
     int64_t launches = 0;
     double ms = 0;
@@ -501,6 +501,19 @@ struct fg_handle {
     int64_t lo_known = 0;
     DevBuf lo_key, lo_ts, lo_val, lo_null, lo_words, lo_cnt, lo_base;
     HostBuf lo_h_key, lo_h_ts, lo_h_val, lo_h_null, lo_h_words;
+    // Window Top-N (fg_set_fired_topn, fg_topn.hip): topn_n > 0 -- every call that returns rows hands
+    // back, per window, the topn_n rows ranking first by agg[topn_agg], gathered into the second
+    // column set t_* (tp_n rows; out_n stays the number of fired rows). The run marks are kept while
+    // it is on, run mode or not: the directory tells the windows of a call without reading a row.
+    int32_t topn_n = 0, topn_agg = 0;
+    bool topn_desc = false;
+    bool tp_listed = false;     // the selection was on at some time: fg_kernel_stats lists the class topn
+    int64_t tp_n = 0;
+    DevBuf t_key, t_ws, t_we, t_null, t_rt;
+    DevBuf t_agg[FG_MAX_AGGS];
+    DevBuf tp_desc, tp_err;
+    DevBuf tp_list[2][4];       // candidate and merged lists: value words, key words, rows, counts
+    HostBuf tp_h_desc, tp_h_err;
 
     // stats
     int64_t records_in = 0, rows_fired = 0, flushes = 0;
@@ -582,7 +595,9 @@ struct KTimer {
     int64_t records;
     hipEvent_t a = nullptr, b = nullptr;
     KTimer(fg_handle* hh, int c, int64_t r) : h(hh), cls(c), records(r) {
-        if (h->timing && ((h->timing_mask >> cls) & 1u)) {
+        // (the mask's bit i is entry i of fg_kernel_stats' list: topn moves up where late_out is not listed)
+        const int bit = cls == K_TOPN && !h->lo_listed ? cls - 1 : cls;
+        if (h->timing && ((h->timing_mask >> bit) & 1u)) {
             a = ev_get(h);
             b = ev_get(h);
             g_launch_ev.start = a;
@@ -1212,7 +1227,7 @@ int runs_directory(fg_handle* h) {
     h->rd_rt.clear();
     h->rd_first.clear();
     h->rd_rows.clear();
-    if (!h->fired_runs) return FG_OK;
+    if (!h->fired_runs && h->topn_n == 0) return FG_OK;
     if (h->run_fail) return h->fail(FG_EDEVICE, "fired runs: a run mark could not be queued");
     int64_t prev = 0;
     for (size_t r = 0; r < h->runs.size(); r++) {
@@ -1262,6 +1277,7 @@ void fill_emit(fg_handle* h, MergeParams& p, int64_t wend) {
     p.out_ws = h->o_ws.as<int64_t>();
     p.out_we = h->o_we.as<int64_t>();
     p.out_rowtime = h->cfg.mode == FG_MODE_DATASTREAM ? h->o_rt.as<int64_t>() : nullptr;
+    if (h->topn_n > 0) run_note(h, p.wstart, wend);   // (the selection takes a call's windows from the marks)
 }
 
 bool staged_any(const fg_handle* h) {
@@ -2415,8 +2431,20 @@ int refire(fg_handle* h, int64_t wm) {
     return FG_OK;
 }
 
+// the columns a call hands back: the fired rows, or with fg_set_fired_topn the selected ones
+struct FiredCols {
+    int64_t n;
+    const DevBuf *key, *ws, *we, *null, *rt, *agg;
+};
+FiredCols fired_cols(const fg_handle* h) {
+    if (h->topn_n > 0) return FiredCols{h->tp_n, &h->t_key, &h->t_ws, &h->t_we, &h->t_null, &h->t_rt, h->t_agg};
+    return FiredCols{h->out_n, &h->o_key, &h->o_ws, &h->o_we, &h->o_null, &h->o_rt, h->o_agg};
+}
+
 int copy_out_to_host(fg_handle* h, fg_rows* r) {
-    const int64_t n = h->out_n;
+    const FiredCols c = fired_cols(h);
+    const int64_t n = c.n;
+    r->n = n;
     const size_t b8 = 8 * (size_t)std::max<int64_t>(n, 1);
     const bool win = !h->fired_runs;   // (run mode: the window columns exist on neither side)
     const bool rt = win && h->cfg.mode == FG_MODE_DATASTREAM;
@@ -2429,15 +2457,15 @@ int copy_out_to_host(fg_handle* h, fg_rows* r) {
     if (rt) HIPCHK(h, h->h_rt.ensure(b8));
     for (int a = 0; a < h->cfg.num_aggs; a++) HIPCHK(h, h->h_agg[a].ensure(b8));
     if (n > 0) {
-        HIPCHK(h, hipMemcpyAsync(h->h_key.p, h->o_key.p, 8 * n, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->h_key.p, c.key->p, 8 * n, hipMemcpyDeviceToHost, h->stream));
         if (win) {
-            HIPCHK(h, hipMemcpyAsync(h->h_ws.p, h->o_ws.p, 8 * n, hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(h, hipMemcpyAsync(h->h_we.p, h->o_we.p, 8 * n, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipMemcpyAsync(h->h_ws.p, c.ws->p, 8 * n, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipMemcpyAsync(h->h_we.p, c.we->p, 8 * n, hipMemcpyDeviceToHost, h->stream));
         }
-        HIPCHK(h, hipMemcpyAsync(h->h_null.p, h->o_null.p, n, hipMemcpyDeviceToHost, h->stream));
-        if (rt) HIPCHK(h, hipMemcpyAsync(h->h_rt.p, h->o_rt.p, 8 * n, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->h_null.p, c.null->p, n, hipMemcpyDeviceToHost, h->stream));
+        if (rt) HIPCHK(h, hipMemcpyAsync(h->h_rt.p, c.rt->p, 8 * n, hipMemcpyDeviceToHost, h->stream));
         for (int a = 0; a < h->cfg.num_aggs; a++)
-            HIPCHK(h, hipMemcpyAsync(h->h_agg[a].p, h->o_agg[a].p, 8 * n, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipMemcpyAsync(h->h_agg[a].p, c.agg[a].p, 8 * n, hipMemcpyDeviceToHost, h->stream));
         int rc = sync(h);
         if (rc) return rc;
     }
@@ -2447,6 +2475,146 @@ int copy_out_to_host(fg_handle* h, fg_rows* r) {
     r->null_mask = h->h_null.as<uint8_t>();
     r->rowtime = rt ? h->h_rt.as<int64_t>() : nullptr;
     for (int a = 0; a < h->cfg.num_aggs; a++) r->agg[a] = h->h_agg[a].as<int64_t>();
+    return FG_OK;
+}
+
+// ---- Window Top-N over the fired rows (fg_set_fired_topn) --------------------
+// The rows [0, out_n) a call is about to return, reduced per window to the topn_n rows ranking
+// first: the directory runs_directory just built (a window may hold several runs) gives the
+// chunks, groups and windows of launch_topn; afterwards the directory lists the selected rows, one
+// run per window, ascending window_end. Three launches on the handle's stream, then one wait.
+int topn_apply(fg_handle* h) {
+    h->tp_n = 0;
+    if (h->topn_n == 0 || h->out_n == 0) return FG_OK;
+    if (h->out_n >= ((int64_t)1 << 31))
+        return h->fail(FG_EINVAL, "fired top-n: %lld fired rows in one call (fewer than 2^31)", (long long)h->out_n);
+    const int32_t n = h->topn_n;
+    struct Win {
+        int64_t wstart = 0, rows = 0;
+        std::vector<std::pair<int64_t, int64_t>> runs;
+    };
+    std::map<int64_t, Win> wins;   // by window_end, ascending
+    for (size_t r = 0; r < h->rd_we.size(); r++) {
+        Win& w = wins[h->rd_we[r]];
+        w.wstart = h->rd_ws[r];
+        w.rows += h->rd_rows[r];
+        w.runs.emplace_back(h->rd_first[r], h->rd_rows[r]);
+    }
+    std::vector<TopnSeg> segs;
+    std::vector<TopnRange> groups;
+    std::vector<TopnWin> tw;
+    int64_t out = 0;
+    for (const auto& kv : wins) {
+        const Win& w = kv.second;
+        const int32_t c0 = (int32_t)segs.size();
+        for (const auto& run : w.runs)
+            for (int64_t at = 0; at < run.second; at += kTopnChunk)
+                segs.push_back(TopnSeg{run.first + at, (int32_t)std::min<int64_t>(kTopnChunk, run.second - at), 0});
+        const int32_t c1 = (int32_t)segs.size(), g0 = (int32_t)groups.size();
+        for (int32_t c = c0; c < c1; c += kTopnGroup) groups.push_back(TopnRange{c, std::min(c + kTopnGroup, c1)});
+        TopnWin t{};
+        t.begin = g0;
+        t.end = (int32_t)groups.size();
+        t.out_rows = (int32_t)std::min<int64_t>(n, w.rows);
+        t.out_first = out;
+        out += t.out_rows;
+        tw.push_back(t);
+    }
+    // descriptors: one pinned block, one copy
+    const size_t o_seg = 0, o_grp = o_seg + sizeof(TopnSeg) * segs.size();
+    const size_t o_win = (o_grp + sizeof(TopnRange) * groups.size() + 15) & ~size_t(15);
+    const size_t dbytes = o_win + sizeof(TopnWin) * tw.size();
+    HIPCHK(h, h->tp_h_desc.ensure(dbytes));
+    HIPCHK(h, h->tp_desc.ensure(dbytes));
+    HIPCHK(h, h->tp_err.ensure(8));
+    HIPCHK(h, h->tp_h_err.ensure(8));
+    std::memcpy(h->tp_h_desc.as<char>() + o_seg, segs.data(), sizeof(TopnSeg) * segs.size());
+    std::memcpy(h->tp_h_desc.as<char>() + o_grp, groups.data(), sizeof(TopnRange) * groups.size());
+    std::memcpy(h->tp_h_desc.as<char>() + o_win, tw.data(), sizeof(TopnWin) * tw.size());
+    const size_t lists[2] = {segs.size(), groups.size()};
+    for (int l = 0; l < 2; l++) {
+        HIPCHK(h, h->tp_list[l][0].ensure(8 * lists[l] * (size_t)n));
+        HIPCHK(h, h->tp_list[l][1].ensure(8 * lists[l] * (size_t)n));
+        HIPCHK(h, h->tp_list[l][2].ensure(4 * lists[l] * (size_t)n));
+        HIPCHK(h, h->tp_list[l][3].ensure(4 * lists[l]));
+    }
+    const bool win = !h->fired_runs, rt = win && h->cfg.mode == FG_MODE_DATASTREAM;
+    const size_t b8 = 8 * (size_t)out;
+    HIPCHK(h, h->t_key.ensure(b8));
+    HIPCHK(h, h->t_null.ensure((size_t)out));
+    for (int a = 0; a < h->cfg.num_aggs; a++) HIPCHK(h, h->t_agg[a].ensure(b8));
+    if (win) {
+        HIPCHK(h, h->t_ws.ensure(b8));
+        HIPCHK(h, h->t_we.ensure(b8));
+    }
+    if (rt) HIPCHK(h, h->t_rt.ensure(b8));
+    HIPCHK(h, hipMemcpyAsync(h->tp_desc.p, h->tp_h_desc.p, dbytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(h->tp_err.p, 0, 8, h->stream));
+    Topn p{};
+    p.n = n;
+    p.agg_index = h->topn_agg;
+    p.descending = h->topn_desc ? 1 : 0;
+    const int32_t agg = h->cfg.aggs[h->topn_agg];
+    p.f64 = h->cfg.val_type == FG_VAL_F64 && agg != FG_AGG_COUNT_STAR && agg != FG_AGG_COUNT ? 1 : 0;
+    p.num_aggs = h->cfg.num_aggs;
+    p.n_chunks = (int32_t)segs.size();
+    p.n_groups = (int32_t)groups.size();
+    p.n_windows = (int32_t)tw.size();
+    p.seg = reinterpret_cast<const TopnSeg*>(h->tp_desc.as<char>() + o_seg);
+    p.group = reinterpret_cast<const TopnRange*>(h->tp_desc.as<char>() + o_grp);
+    p.win = reinterpret_cast<const TopnWin*>(h->tp_desc.as<char>() + o_win);
+    p.key = h->o_key.as<int64_t>();
+    p.ord = h->o_agg[h->topn_agg].as<int64_t>();
+    p.null_mask = h->o_null.as<uint8_t>();
+    p.o_key = h->t_key.as<int64_t>();
+    p.o_null = h->t_null.as<uint8_t>();
+    for (int a = 0; a < h->cfg.num_aggs; a++) {
+        p.agg[a] = h->o_agg[a].as<int64_t>();
+        p.o_agg[a] = h->t_agg[a].as<int64_t>();
+    }
+    if (win) {
+        p.ws = h->o_ws.as<int64_t>();
+        p.we = h->o_we.as<int64_t>();
+        p.o_ws = h->t_ws.as<int64_t>();
+        p.o_we = h->t_we.as<int64_t>();
+    }
+    if (rt) {
+        p.rt = h->o_rt.as<int64_t>();
+        p.o_rt = h->t_rt.as<int64_t>();
+    }
+    TopnLists* tl[2] = {&p.cand, &p.merged};
+    for (int l = 0; l < 2; l++) {
+        tl[l]->hi = h->tp_list[l][0].as<unsigned long long>();
+        tl[l]->lo = h->tp_list[l][1].as<unsigned long long>();
+        tl[l]->ix = h->tp_list[l][2].as<uint32_t>();
+        tl[l]->cnt = h->tp_list[l][3].as<uint32_t>();
+    }
+    p.err = h->tp_err.as<unsigned long long>();
+    {
+        KTimer kt(h, K_TOPN, h->out_n);
+        HIPCHK(h, launch_topn(p, h->stream));
+    }
+    HIPCHK(h, hipMemcpyAsync(h->tp_h_err.p, h->tp_err.p, 8, hipMemcpyDeviceToHost, h->stream));
+    if (int rc = sync(h)) return rc;
+    if (*h->tp_h_err.as<unsigned long long>() != 0)
+        return h->fail(FG_EDEVICE, "internal: fired top-n selected a different number of rows than the directory gives");
+    h->kstat[K_TOPN].rows += out;
+    h->tp_n = out;
+    // the directory of the selected rows: one run per window
+    h->rd_ws.clear();
+    h->rd_we.clear();
+    h->rd_rt.clear();
+    h->rd_first.clear();
+    h->rd_rows.clear();
+    size_t i = 0;
+    for (const auto& kv : wins) {
+        h->rd_ws.push_back(kv.second.wstart);
+        h->rd_we.push_back(kv.first);
+        h->rd_rt.push_back(jsub(kv.first, 1));
+        h->rd_first.push_back(tw[i].out_first);
+        h->rd_rows.push_back(tw[i].out_rows);
+        i++;
+    }
     return FG_OK;
 }
 
@@ -4352,16 +4520,17 @@ int fg_advance_progress_async_n(fg_handle* h, const int64_t* wms, int64_t n) {
 }
 
 static void device_rows(fg_handle* h, int32_t out_location, fg_rows* fired) {
+    const FiredCols c = fired_cols(h);
     std::memset(fired, 0, sizeof *fired);
-    fired->n = h->out_n;
+    fired->n = c.n;
     fired->num_aggs = h->cfg.num_aggs;
     fired->location = out_location;
-    fired->key = h->o_key.as<int64_t>();
-    fired->window_start = h->fired_runs ? nullptr : h->o_ws.as<int64_t>();
-    fired->window_end = h->fired_runs ? nullptr : h->o_we.as<int64_t>();
-    fired->null_mask = h->o_null.as<uint8_t>();
-    fired->rowtime = h->cfg.mode == FG_MODE_DATASTREAM && !h->fired_runs ? h->o_rt.as<int64_t>() : nullptr;
-    for (int a = 0; a < h->cfg.num_aggs; a++) fired->agg[a] = h->o_agg[a].as<int64_t>();
+    fired->key = c.key->as<int64_t>();
+    fired->window_start = h->fired_runs ? nullptr : c.ws->as<int64_t>();
+    fired->window_end = h->fired_runs ? nullptr : c.we->as<int64_t>();
+    fired->null_mask = c.null->as<uint8_t>();
+    fired->rowtime = h->cfg.mode == FG_MODE_DATASTREAM && !h->fired_runs ? c.rt->as<int64_t>() : nullptr;
+    for (int a = 0; a < h->cfg.num_aggs; a++) fired->agg[a] = c.agg[a].as<int64_t>();
 }
 
 int fg_collect_fired_to(fg_handle* h, int32_t out_location, fg_rows* fired) {
@@ -4375,6 +4544,7 @@ int fg_collect_fired_to(fg_handle* h, int32_t out_location, fg_rows* fired) {
     }
     h->async_open = false;
     if (int rc = runs_directory(h)) return rc;
+    if (int rc = topn_apply(h)) return rc;
     if (out_location == FG_HOST) {
         std::memset(fired, 0, sizeof *fired);
         fired->n = h->out_n;
@@ -4417,6 +4587,8 @@ int fg_advance_progress(fg_handle* h, int64_t wm, int32_t out_location, fg_rows*
     h->rows_fired += h->out_n - h->adv_base;   // (the async rows were counted by their advances)
     h->async_open = false;
     rc = runs_directory(h);
+    if (rc) return rc;
+    rc = topn_apply(h);
     if (rc) return rc;
     if (fired) {
         std::memset(fired, 0, sizeof *fired);
@@ -4756,6 +4928,34 @@ int fg_set_fired_runs(fg_handle* h, int32_t on) {
             b->bytes = 0;
         }
     }
+    runs_clear(h);
+    return runs_directory(h);
+}
+
+int fg_set_fired_topn(fg_handle* h, int32_t n, int32_t agg_index, int32_t descending) {
+    if (!h) return FG_EINVAL;
+    h->snap.plan_valid = false;
+    if (n < 0 || n > FG_TOPN_MAX) return h->fail(FG_EINVAL, "fg_set_fired_topn: n = %d is not in 0 .. %d", n, FG_TOPN_MAX);
+    if (n > 0) {
+        if (agg_index < 0 || agg_index >= h->cfg.num_aggs)
+            return h->fail(FG_EINVAL, "fg_set_fired_topn: agg_index %d is not in 0 .. %d", agg_index, h->cfg.num_aggs - 1);
+        if (h->local)
+            return h->fail(FG_EINVAL, "fg_set_fired_topn: a FG_FLAG_LOCAL_PARTIALS handle's rows are partial accumulators, "
+                                      "not results");
+        if (h->lateness > 0)
+            return h->fail(FG_EINVAL, "fg_set_fired_topn: allowed_lateness_ms > 0 re-fires single rows, and an update row "
+                                      "is not a rank input");
+    }
+    if (h->fire_pending) return h->fail(FG_ESTATE, "fg_set_fired_topn: a fire is pending (fg_collect_fired first)");
+    if (h->async_open || h->late_rows > 0)
+        return h->fail(FG_ESTATE, "fg_set_fired_topn: fired rows are not collected yet (fg_collect_fired first)");
+    if (n == 0 && h->topn_n == 0) return FG_OK;
+    h->topn_n = n;
+    h->topn_agg = n > 0 ? agg_index : 0;
+    h->topn_desc = n > 0 && descending != 0;
+    if (n > 0) h->tp_listed = true;
+    h->out_n = 0;
+    h->tp_n = 0;
     runs_clear(h);
     return runs_directory(h);
 }
@@ -5320,19 +5520,24 @@ int fg_kernel_stats(fg_handle* h, fg_kernel_stat* out, int32_t max, int32_t* cou
     if (int rc0 = settle_pending(h)) return rc0;
     int rc = sync(h, true);
     if (rc) return rc;
-    // (late_out, the last class, is listed for handles that had the late output on: the list of every
-    // other handle is what it was before the class existed)
-    const int nclass = h->lo_listed ? K_NCLASS : K_NCLASS - 1;
-    static_assert(K_LATE_OUT == K_NCLASS - 1, "late_out is the last class");
-    *count = nclass;
-    for (int c = 0; c < nclass && c < max; c++) {
-        std::memset(&out[c], 0, sizeof(fg_kernel_stat));
-        std::snprintf(out[c].name, sizeof out[c].name, "%s", kClassName[c]);
-        out[c].launches = h->kstat[c].launches;
-        out[c].total_ms = h->kstat[c].ms;
-        out[c].records = h->kstat[c].records;
-        out[c].rows = h->kstat[c].rows;
+    // (late_out is listed for handles that had the late output on, topn -- after it -- for handles
+    // that had the selection on: the list of every other handle is what it was before the classes
+    // existed)
+    static_assert(K_LATE_OUT == K_NCLASS - 2 && K_TOPN == K_NCLASS - 1, "late_out and topn are the last classes");
+    int at = 0;
+    for (int c = 0; c < K_NCLASS; c++) {
+        if ((c == K_LATE_OUT && !h->lo_listed) || (c == K_TOPN && !h->tp_listed)) continue;
+        if (at < max) {
+            std::memset(&out[at], 0, sizeof(fg_kernel_stat));
+            std::snprintf(out[at].name, sizeof out[at].name, "%s", kClassName[c]);
+            out[at].launches = h->kstat[c].launches;
+            out[at].total_ms = h->kstat[c].ms;
+            out[at].records = h->kstat[c].records;
+            out[at].rows = h->kstat[c].rows;
+        }
+        at++;
     }
+    *count = at;
     return FG_OK;
 }
 

@@ -660,4 +660,59 @@ struct KgParams {
 hipError_t launch_kg_count(const KgParams& p, hipStream_t s);
 hipError_t launch_kg_scatter(const KgParams& p, hipStream_t s);
 
+// Window Top-N over the fired rows (fg_set_fired_topn, fg_topn.hip): per window of the rows a call
+// returns, the n rows ranking first by one aggregate, gathered into a second column set. The host
+// cuts every run of the fired-row directory into chunks (never across a window), groups a window's
+// chunks and lists the windows by ascending window_end with their output offsets.
+constexpr int kTopnMax = 1024;                // FG_TOPN_MAX
+constexpr int kTopnChunk = 16384;             // rows per workgroup of the candidate pass
+constexpr int kTopnGroup = 32;                // candidate lists per workgroup of the merge pass
+struct TopnSeg {                 // a chunk: rows [first, first + rows) of the fired rows, all of one window
+    int64_t first;
+    int32_t rows;                // 1 .. kTopnChunk
+    int32_t reserved0;
+};
+struct TopnRange {               // a group: the candidate lists (chunks) [begin, end) of one window
+    int32_t begin, end;
+};
+struct TopnWin {                 // a window: its merged lists (groups) [begin, end) and its selected rows
+    int32_t begin, end;
+    int32_t out_rows;            // min(n, rows of the window)
+    int32_t reserved0;
+    int64_t out_first;           // the exclusive prefix of out_rows over the windows
+};
+struct TopnLists {               // candidate lists of n entries each: (value word, key word, side | row)
+    unsigned long long* hi;
+    unsigned long long* lo;
+    uint32_t* ix;
+    uint32_t* cnt;               // [lists] entries of each list (<= n)
+};
+struct Topn {
+    int32_t n, agg_index, descending, f64;   // f64: the order column holds DOUBLE bits
+    int32_t num_aggs;
+    int32_t n_chunks, n_groups, n_windows;
+    const TopnSeg* seg;          // [n_chunks] grouped by window
+    const TopnRange* group;      // [n_groups] grouped by window
+    const TopnWin* win;          // [n_windows] ascending window_end
+    // the fired rows (fewer than 2^31); ws / we / rt NULL where the handle has no such column
+    const int64_t* key;
+    const int64_t* ord;          // agg[agg_index]
+    const uint8_t* null_mask;
+    const int64_t* agg[kMaxAggs];
+    const int64_t* ws;
+    const int64_t* we;
+    const int64_t* rt;
+    TopnLists cand;              // [n_chunks * n] the candidate pass's lists
+    TopnLists merged;            // [n_groups * n] the merge pass's lists
+    // the selected rows
+    int64_t* o_key;
+    int64_t* o_agg[kMaxAggs];
+    uint8_t* o_null;
+    int64_t* o_ws;
+    int64_t* o_we;
+    int64_t* o_rt;
+    unsigned long long* err;     // [0] set when a window's selection disagrees with out_rows (never)
+};
+hipError_t launch_topn(const Topn& p, hipStream_t s);   // candidates, merge, final + gather
+
 }  // namespace fg

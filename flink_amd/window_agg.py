@@ -85,8 +85,12 @@ class WindowAggOperator:
                  key_group_range=(0, 127), kernel_timing: bool = False, local_partials: bool = False,
                  proctime: bool = False, zone: str | None = None, windowed: bool = False,
                  allowed_lateness: int = 0, purging_trigger: bool = False, fired_runs: bool = False,
-                 late_output: bool = False):
+                 late_output: bool = False, topn=None):
         """fired_runs: run mode (fg_set_fired_runs, see set_fired_runs).
+
+        topn: (n, agg, descending) -- Window Top-N on the GPU (fg_set_fired_topn, see
+        set_fired_topn): every call that returns rows returns, per fired window, the n rows
+        ranking first by the aggregate `agg` (a name of `aggs`, or its index).
 
         late_output (DataStream): WindowedStream.sideOutputLateData -- late elements are kept and
         returned by collect_late() instead of being counted (fg_set_late_output, see
@@ -173,6 +177,8 @@ class WindowAggOperator:
                 self.set_fired_runs(True)
             if late_output:
                 self.set_late_output(True)
+            if topn is not None:
+                self.set_fired_topn(*topn)
         except Exception:
             self.close()
             raise
@@ -424,6 +430,29 @@ class WindowAggOperator:
                 return np.zeros(0, dtype=np.int64)
             return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_int64)), shape=(n,)).copy()
         return {k: col(getattr(rr, k)) for k in RUN_COLUMNS}
+
+    # -- Window Top-N ---------------------------------------------------------------------------
+    def set_fired_topn(self, n: int, agg=0, descending: bool = True):
+        """fg_set_fired_topn: ROW_NUMBER() OVER (PARTITION BY window_start, window_end ORDER BY agg
+        [DESC]) <= n, selected on the GPU -- process_watermark and collect_fired return, per fired
+        window, only the n rows that rank first by `agg` (a name of the operator's `aggs` such as
+        "count", or an index into them); windows come by ascending window_end and a window's rows in
+        rank order (row i is ROW_NUMBER i + 1). BIGINT columns compare as signed integers, DOUBLE
+        columns in Double.compare's order (-0.0 below +0.0, NaN above +inf); a NULL aggregate is the
+        smallest value; ties go to the smaller key. n = 0 turns the selection off. The structured
+        array, device FgRows and fired_runs() keep their form. Refused (WindowSpecError) for n
+        outside 0 .. 1024, an unknown aggregate, a local_partials operator and allowed_lateness > 0,
+        and (FlinkGpuError, FG_ESTATE) while fired rows are not collected."""
+        if int(n) == 0:
+            idx = 0
+        elif isinstance(agg, str):
+            if agg not in AGGS or AGGS[agg] not in self.aggs:
+                raise L.WindowSpecError(f"set_fired_topn: the operator has no aggregate {agg!r} "
+                                        f"(its aggregates: {', '.join(AGG_NAMES[a] for a in self.aggs)})")
+            idx = self.aggs.index(AGGS[agg])
+        else:
+            idx = int(agg)
+        L.check(self._lib.fg_set_fired_topn(self._h, int(n), idx, 1 if descending else 0), self._h)
 
     # -- late elements as a side output -----------------------------------------------------------
     def set_late_output(self, on: bool = True):

@@ -32,6 +32,8 @@
  *   SlicingWindowOperator.getNumLateRecordsDropped :300-303            fg_late_dropped
  *   WindowedStream.sideOutputLateData -> WindowOperator.processElement :448-456
  *     (sideOutput(element) instead of numLateRecordsDropped.inc())      fg_set_late_output, fg_collect_late
+ *   WindowRankOperator above the window aggregate (Window Top-N: ROW_NUMBER() OVER (PARTITION BY
+ *     window_start, window_end ORDER BY agg) <= N), its local rank                 fg_set_fired_topn
  *   two-phase: LocalAggCombiner.combine (local operator output)        fg_config.flags |= FG_FLAG_LOCAL_PARTIALS
  *     GlobalAggCombiner.combine  .../combines/GlobalAggCombiner.java:77-110  fg_add_partials
  *   WindowBuffer.close / SlicingWindowOperator.close :178-183           fg_close
@@ -455,8 +457,8 @@ int  fg_fired_runs(fg_handle* h, fg_row_runs* out);
  * rows, state, snapshots, records_in and every other statistic are what they are with the mode off.
  * The records are copied out on the device by a pass of their own ahead of the ingest
  * (fg_kernel_stats class "late_out": records = the batches' elements, rows = the late records; the
- * class follows every other class, and fg_kernel_stats lists it for a handle once the mode was turned
- * on); the host reads nothing during fg_add_batch.
+ * class follows every other class but "topn" (fg_set_fired_topn), and fg_kernel_stats lists it for a
+ * handle once the mode was turned on); the host reads nothing during fg_add_batch.
  * fg_collect_late: the late records of all batches since the previous collect (or since fg_open,
  * fg_reset, fg_restore*), in arrival order -- batch by batch, inside a batch by index, as the reference
  * emits them one by one in processElement. rowtime is the element's timestamp as it was handed in
@@ -482,6 +484,62 @@ typedef struct fg_late_records {
 } fg_late_records;
 int  fg_set_late_output(fg_handle* h, int32_t on);
 int  fg_collect_late(fg_handle* h, int32_t out_location, fg_late_records* out);
+/* Top-N rows per fired window (ABI 16, added): Flink's Window Top-N directly above the window
+ * aggregate, ROW_NUMBER() OVER (PARTITION BY window_start, window_end ORDER BY agg [DESC]) <= n, selected
+ * where the fired rows sit instead of after their copy to the host. At parallelism P the P x n rows
+ * the handles return are a superset of the global top n (the local rank of the reference's plan); the
+ * global rank over them stays with the caller.
+ * fg_set_fired_topn(h, n, agg_index, descending): n = 0 turns the selection off (the default;
+ * agg_index and descending are then ignored; idempotent). n in 1 .. FG_TOPN_MAX: every call that
+ * returns fg_rows -- fg_advance_progress, fg_collect_fired, fg_collect_fired_to -- returns, per fired
+ * window, only the n rows that rank first by agg[agg_index].
+ *  - Rank order, a total order (results are deterministic). Primary: agg[agg_index] compared as the
+ *    column's SQL type -- BIGINT (COUNT(*), COUNT, and SUM / AVG / SUM0 / MIN / MAX of a BIGINT value)
+ *    as signed 64-bit; DOUBLE (SUM / AVG / SUM0 / MIN / MAX of a DOUBLE value) in Double.compare's
+ *    order: -0.0 below +0.0, NaN (every NaN alike) above +inf. descending != 0: the largest first. A
+ *    NULL aggregate (its null_mask bit) is the smallest value: last when descending, first when
+ *    ascending (Flink's default null collation, NULLs low). Ties: the smaller key (signed) ranks
+ *    first -- the engine's choice; ROW_NUMBER in the reference breaks ties by arrival order at the
+ *    rank operator, which a keyBy leaves unspecified.
+ *  - The selection is per window, not per run: it is applied to the complete set of rows the call
+ *    hands back, grouped by window_end -- the rows of uncollected fg_advance_progress_async calls
+ *    that lead a synchronous advance included, and a window whose rows sit in several runs
+ *    (fg_fired_runs) is selected once. Without allowed lateness all rows a watermark fires for a
+ *    window, the rows a split region re-emits included, are complete before any call returns them,
+ *    so a window's rows never straddle two returning calls. (After fg_restore* a HOP / CUMULATE
+ *    window that fired before the checkpoint may fire again for the keys of later records: those
+ *    rows are a set of their own, selected as the call returns them.)
+ *  - Output order: windows by ascending window_end; inside a window by rank -- row i of a window is
+ *    ROW_NUMBER = i + 1. A window with fewer than n rows returns all of them, ranked.
+ *  - fg_rows.n is the selected count; key, agg[], null_mask and, when run mode is off, window_start,
+ *    window_end and rowtime are gathered for the selected rows, for FG_DEVICE and FG_HOST alike. With
+ *    FG_HOST only the selected rows are copied to the host. The FG_DEVICE columns are complete when
+ *    the call returns.
+ *  - Run mode (fg_set_fired_runs) composes: fg_fired_runs describes the selected rows, exactly
+ *    one run per window, and its invariants hold (first_row[0] = 0, contiguous runs, every
+ *    rows[i] > 0, the rows sum to fg_rows.n).
+ *  - fg_stats.rows_fired, fg_late_dropped, state, snapshots and restore are what they are with the
+ *    selection off. fg_kernel_stats class "topn": records = rows in, rows = rows out; listed for a
+ *    handle once the selection was turned on, after "late_out" when both are listed
+ *    (fg_set_kernel_timing's bit i is entry i of the list as fg_kernel_stats returns it).
+ *  - FG_EINVAL (fg_last_error names the reason; the handle stays usable): n < 0 or n > FG_TOPN_MAX;
+ *    and turning on: agg_index outside 0 .. num_aggs - 1; a FG_FLAG_LOCAL_PARTIALS handle -- its rows
+ *    are partial accumulators, not results; allowed_lateness_ms > 0 -- late elements re-fire single
+ *    rows, and an update row is not a rank input. A returning call with 2^31 or more fired rows
+ *    fails with FG_EINVAL while the selection is on.
+ *  - FG_ESTATE: fired rows are not collected yet, or a fire is pending (after
+ *    fg_advance_progress_async: fg_collect_fired first) -- the rule of fg_set_fired_runs.
+ *  - The pass runs as three kernel launches per returning call (whatever the number of windows) on the
+ *    handle's stream, after the fires have completed and before the row copy; per fired row it reads
+ *    the order column, its null_mask byte and the key (17 B), and every column of the selected rows
+ *    only. While the selection is on the engine keeps the run marks of fg_fired_runs also with run mode
+ *    off (one small launch per window change), so that the host knows a call's windows without
+ *    reading a row.
+ *  - Extra device memory, allocated by the first selecting call and kept until fg_close: candidate
+ *    buffers of 20 B x n per 16,384 fired rows (plus 1/32 of that for the merged lists), and a second
+ *    set of the output columns sized by n x (windows per call), not by the fired rows. */
+#define FG_TOPN_MAX 1024
+int  fg_set_fired_topn(fg_handle* h, int32_t n, int32_t agg_index, int32_t descending);
 /* Selective images (ABI 16, added): a checkpoint that exports and copies only the slices its caller
  * needs. The engine says what is resident and what changed (plan), the caller answers with a mask
  * (a shim's policy needs more than the changed slices: a CUMULATE namespace is rebuilt from all its

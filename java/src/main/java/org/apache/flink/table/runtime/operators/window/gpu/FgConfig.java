@@ -64,6 +64,28 @@ public final class FgConfig {
     public static boolean firedRuns = Boolean.getBoolean("flinkgpu.firedRuns");
 
     /**
+     * Window Top-N on the GPU (fg_set_fired_topn), "n,column,order": "10,1,desc" keeps, per fired
+     * window, the 10 rows ranking first by output aggregate 1, descending ("asc": ascending). Set by
+     * the planner for a WindowRank partitioned by the window directly above the window aggregate
+     * (INTEGRATION.md section 4); unset or n = 0: off.
+     */
+    public static final String FIRED_TOPN_KEY = "table.exec.window-agg.gpu.fired-topn";
+    public static String firedTopN = System.getProperty(FIRED_TOPN_KEY);
+
+    /** {n, aggIndex, descending ? 1 : 0} of a fired-topn value; null when unset or n = 0 */
+    public static int[] parseFiredTopN(String v) {
+        if (v == null || v.trim().isEmpty()) {
+            return null;
+        }
+        String[] f = v.trim().split("\\s*,\\s*");
+        if (f.length != 3 || !(f[2].equalsIgnoreCase("asc") || f[2].equalsIgnoreCase("desc"))) {
+            throw new IllegalArgumentException(FIRED_TOPN_KEY + ": expected n,column,asc|desc, got " + v);
+        }
+        int n = Integer.parseInt(f[0]);
+        return n == 0 ? null : new int[] {n, Integer.parseInt(f[1]), f[2].equalsIgnoreCase("desc") ? 1 : 0};
+    }
+
+    /**
      * When a checkpoint retires the keys of the dictionary that hold no state (fg_key_dict_retain;
      * STRING / multi-column / NULL keys only): at a barrier where the dictionary's live keys are at
      * least 2^16 and more than dictRetainFactor x the rows of state the snapshot plan lists. Such a

@@ -105,6 +105,15 @@ public final class FlinkGpu {
     public static native long[] firedRuns(long h);
 
     /**
+     * fg_set_fired_topn (ABI 16): Window Top-N on the GPU -- advanceProgress and collectFired
+     * return, per fired window, only the n rows ranking first by agg[aggIndex] (windows by ascending
+     * end, rows in rank order; NULL smallest, ties to the smaller key); n = 0 turns it off. Refused
+     * for FG_FLAG_LOCAL_PARTIALS handles and with allowed lateness (IllegalArgumentException), and
+     * while fired rows are uncollected.
+     */
+    public static native void setFiredTopN(long h, int n, int aggIndex, boolean descending);
+
+    /**
      * fg_set_late_output (ABI 16): WindowedStream.sideOutputLateData -- every element the handle
      * would count in {@link #lateDropped} is kept instead and returned by {@link #collectLate}; the
      * counter does not move. DataStream handles only (IllegalArgumentException otherwise); turning

@@ -132,6 +132,10 @@ public final class GpuSlicingWindowAggOperator extends TableStreamOperator<RowDa
                         return rc;
                     }
                 });
+        int[] topN = FgConfig.parseFiredTopN(FgConfig.firedTopN);
+        if (topN != null) {   // the local rank of a WindowRank directly above this operator
+            processor.setFiredTopN(topN[0], topN[1], topN[2] != 0);
+        }
     }
 
     @Override

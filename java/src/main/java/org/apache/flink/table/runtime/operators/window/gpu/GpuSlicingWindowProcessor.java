@@ -269,6 +269,11 @@ public final class GpuSlicingWindowProcessor implements SlicingWindowProcessor<L
         return b;
     }
 
+    /** Window Top-N on the open handle (fg_set_fired_topn; FgConfig.FIRED_TOPN_KEY) */
+    void setFiredTopN(int n, int aggIndex, boolean descending) {
+        FlinkGpu.setFiredTopN(handle, n, aggIndex, descending);
+    }
+
     // ---- progress ---------------------------------------------------------------------------
 
     @Override

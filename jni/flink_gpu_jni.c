@@ -268,6 +268,15 @@ JNIEXPORT void JNICALL FN(setFiredRuns)(JNIEnv* env, jclass cls, jlong hp, jbool
     (void)check(env, h, fg_set_fired_runs(h, on ? 1 : 0));
 }
 
+/* void setFiredTopN(long h, int n, int aggIndex, boolean descending): Window Top-N on the GPU
+ * (fg_set_fired_topn, ABI 16) -- advanceProgress / collectFired return, per fired window, the n rows
+ * ranking first by agg[aggIndex]; n = 0 turns it off */
+JNIEXPORT void JNICALL FN(setFiredTopN)(JNIEnv* env, jclass cls, jlong hp, jint n, jint agg_index, jboolean descending) {
+    (void)cls;
+    fg_handle* h = (fg_handle*)(intptr_t)hp;
+    (void)check(env, h, fg_set_fired_topn(h, (int32_t)n, (int32_t)agg_index, descending ? 1 : 0));
+}
+
 /* long[] firedRuns(long h): the runs of the rows the last advanceProgress / collectFired returned
  * (fg_fired_runs) as one array: [n, window_start[n], window_end[n], first_row[n], rows[n]] -- run i
  * covers rows [first_row[i], first_row[i] + rows[i]); its rowtime is window_end[i] - 1. A window may
