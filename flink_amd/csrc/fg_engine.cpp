@@ -739,33 +739,49 @@ int zero_scalars(fg_handle* h, bool with_out) {
     return FG_OK;
 }
 
-// Every tile fire goes through here. FG_STAMPS builds with FG_STAMPS set in the environment print
-// the fire's phase cycles per wave (k_tile_fire's FSTAMP phases) after each launch.
-hipError_t tile_fire_launch(fg_handle* h, TileFire& f, int32_t workgroups, hipStream_t s) {
+// The FG_STAMPS bracket of a launch: FG_STAMPS builds with FG_STAMPS set in the environment print
+// the phase cycles per wave its kernels stamped (k_tile_fire's FSTAMP phases, the merges' four)
+// after the launch. arm() before it gives the zeroed stamp words for the launch's parameters
+// (MergeParams.stamps; null -- always, in a regular build -- when off), report() after it reads
+// them back (a synchronization) and hands them to `print`. Brackets do not nest: one buffer.
+struct Stamps {
+    hipStream_t s;
+    unsigned long long* words = nullptr;
+    explicit Stamps(hipStream_t stream) : s(stream) {}
+    unsigned long long* arm() {
 #ifdef FG_STAMPS
-    static DevBuf d_fs;
-    const bool st = getenv("FG_STAMPS") != nullptr && d_fs.ensure(64) == hipSuccess;
-    if (st) {
-        (void)hipMemsetAsync(d_fs.p, 0, 64, s);
-        f.m.stamps = d_fs.as<unsigned long long>();
+        static DevBuf d;
+        if (getenv("FG_STAMPS") != nullptr && d.ensure(64) == hipSuccess) {
+            (void)hipMemsetAsync(d.p, 0, 64, s);
+            words = d.as<unsigned long long>();
+        }
+#endif
+        return words;
     }
-    const hipError_t e = launch_tile_fire(f, workgroups, s);
-    if (st) {
+    template <class Print>
+    void report(Print print) {
+        if (!words) return;
         unsigned long long v[8];
-        (void)hipMemcpyAsync(v, d_fs.p, sizeof v, hipMemcpyDeviceToHost, s);
+        (void)hipMemcpyAsync(v, words, sizeof v, hipMemcpyDeviceToHost, s);
         (void)hipStreamSynchronize(s);
+        print(v);
+    }
+};
+
+// Every tile fire goes through here.
+hipError_t tile_fire_launch(fg_handle*, TileFire& f, int32_t workgroups, hipStream_t s) {
+    Stamps st(s);
+    f.m.stamps = st.arm();
+    const hipError_t e = launch_tile_fire(f, workgroups, s);
+    st.report([&](const unsigned long long* v) {
         const double waves = (double)workgroups * kTileFireThreads / 64;
         fprintf(stderr, "[fg stamps] tile_fire split=%d merge=%d srcs=%d dst=%d passes=%d: clear %.0f walk %.0f wait %.0f "
                 "insert %.0f sources %.0f barrier %.0f compact %.0f emit %.0f (cycles/wave)\n", f.split, f.merge,
                 f.m.n_src, f.m.has_dst, f.n_passes, v[0] / waves, v[1] / waves, v[2] / waves, v[3] / waves,
                 v[4] / waves, v[5] / waves, v[6] / waves, v[7] / waves);
-        f.m.stamps = nullptr;
-    }
+    });
+    f.m.stamps = nullptr;
     return e;
-#else
-    (void)h;
-    return launch_tile_fire(f, workgroups, s);
-#endif
 }
 
 int check_overflow(fg_handle* h) {
@@ -846,11 +862,38 @@ void set_values(const fg_handle* h, MergeParams* p) {
     for (int a = 0; a < FG_MAX_AGGS; a++) p->agg_slot[a] = h->agg_slot[a];
 }
 
-// MergeParams of job `ji` at the current region bits (the general path; callers pick the
-// fast variants on a first launch)
 // the COUNT(*) of any key stays below 2^32 (the compact merge's u32 counts)
 bool ub_cnt_fits(const fg_handle* h) { return h->cnt_bound < ((int64_t)1 << 32); }
 
+// What the parameters of every launch of job `ji` share, merge or tile fire, at the current region
+// bits: the value accumulators, the source tables (by value up to two, else through the arena),
+// the destination, the scalar words and the job's index for the fail list.
+int job_skeleton(fg_handle* h, int ji, MergeParams* p) {
+    const MergeJob& j = h->jobs[(size_t)ji];
+    p->region_bits = h->region_bits;
+    set_values(h, p);
+    std::vector<TableRef> srcs;
+    for (SliceTable* x : j.srcs) srcs.push_back(ref_of(x));
+    p->n_src = (int)srcs.size();
+    if (srcs.size() <= 2) {   // by value in the arguments (no descriptor copy on the stream)
+        for (size_t i = 0; i < srcs.size(); i++) p->src_in[i] = srcs[i];
+    } else {
+        int rc = arena_put(h, srcs.data(), srcs.size(), &p->src);
+        if (rc) return rc;
+    }
+    p->has_dst = j.dst ? 1 : 0;
+    if (j.dst) p->dst = ref_of(j.dst);
+    p->overflow = h->scalars.as<unsigned int>();
+    p->out_count = reinterpret_cast<unsigned long long*>(h->scalars.as<char>() + 8);
+    p->fail_list = h->fail_list.as<uint32_t>();
+    p->fail_n = reinterpret_cast<uint32_t*>(h->scalars.as<char>() + 4);
+    p->fail_cap = kFailCap;
+    p->job = ji;
+    return FG_OK;
+}
+
+// MergeParams of job `ji` at the current region bits (the general path; callers pick the
+// fast variants on a first launch)
 int job_params(fg_handle* h, int ji, MergeParams* p) {
     const MergeJob& j = h->jobs[(size_t)ji];
     // the general merge writes the wide layout: a narrow destination is widened first (before the
@@ -858,14 +901,12 @@ int job_params(fg_handle* h, int ji, MergeParams* p) {
     if (int rc = widen_table(h, j.dst)) return rc;
     std::vector<StagedBatch> sb;
     for (const JobBatch& jb : j.batches) sb.push_back(batch_of(h, jb));
-    std::vector<TableRef> srcs;
     // sources known free of NULL counts are read without their cnt_null column; a destination
     // may hold NULL counts iff something merged into it may
     unsigned long long null_mask = 0;
     bool dst_null = false;
     bool src_narrow = false, all_narrow = !j.srcs.empty();
     for (size_t i = 0; i < j.srcs.size(); i++) {
-        srcs.push_back(ref_of(j.srcs[i]));
         src_narrow = src_narrow || j.srcs[i]->narrow;
         all_narrow = all_narrow && j.srcs[i]->narrow;
         if (j.srcs[i]->has_null) {
@@ -878,30 +919,14 @@ int job_params(fg_handle* h, int ji, MergeParams* p) {
         dst_null = dst_null || !jb.s || jb.s->has_null || jb.s->is_acc;   // (restore images, partials)
     if (j.dst) j.dst->has_null = j.dst->has_null || dst_null;
     *p = MergeParams{};
-    p->region_bits = h->region_bits;
-    p->n_src = (int)srcs.size();
+    if (int rc = job_skeleton(h, ji, p)) return rc;
     p->src_narrow = all_narrow ? 2 : src_narrow ? 1 : 0;
-    if (srcs.size() <= 2) {   // by value in the arguments (no descriptor copy on the stream)
-        for (size_t i = 0; i < srcs.size(); i++) p->src_in[i] = srcs[i];
-    } else {
-        int rc = arena_put(h, srcs.data(), srcs.size(), &p->src);
-        if (rc) return rc;
-    }
     p->n_batches = (int)sb.size();
     if (!sb.empty()) {
         int rc = arena_put(h, sb.data(), sb.size(), &p->batches);
         if (rc) return rc;
     }
-    set_values(h, p);
-    p->has_dst = j.dst ? 1 : 0;
-    if (j.dst) p->dst = ref_of(j.dst);
     if (j.emit) fill_emit(h, *p, j.wend);
-    p->overflow = h->scalars.as<unsigned int>();
-    p->out_count = reinterpret_cast<unsigned long long*>(h->scalars.as<char>() + 8);
-    p->fail_list = h->fail_list.as<uint32_t>();
-    p->fail_n = reinterpret_cast<uint32_t*>(h->scalars.as<char>() + 4);
-    p->fail_cap = kFailCap;
-    p->job = ji;
     p->mark_mask = j.mark_mask;
     p->markonly_mask = j.markonly_mask;
     p->emit_marked = j.emit_marked;
@@ -932,32 +957,13 @@ int tile_job_params(fg_handle* h, int ji, TileFire* f) {
     for (const JobBatch& jb : j.batches) tps.push_back(tile_pass_of(jb.s, jb.lane));
     *f = TileFire{};
     MergeParams& p = f->m;
-    p.region_bits = h->region_bits;
-    set_values(h, &p);
     if (j.emit) {
         fill_emit(h, p, j.wend);
         p.emit = 1;
     }
-    std::vector<TableRef> srcs;
-    for (SliceTable* x : j.srcs) {
-        srcs.push_back(ref_of(x));
+    if (int rc = job_skeleton(h, ji, &p)) return rc;
+    for (const SliceTable* x : j.srcs)
         if (x->narrow) p.src_narrow = 1;
-    }
-    p.n_src = (int)srcs.size();
-    if (srcs.size() <= 2) {   // by value in the arguments (no descriptor copy on the stream)
-        for (size_t i = 0; i < srcs.size(); i++) p.src_in[i] = srcs[i];
-    } else {
-        int rc = arena_put(h, srcs.data(), srcs.size(), &p.src);
-        if (rc) return rc;
-    }
-    p.has_dst = j.dst ? 1 : 0;
-    if (j.dst) p.dst = ref_of(j.dst);
-    p.overflow = h->scalars.as<unsigned int>();
-    p.out_count = reinterpret_cast<unsigned long long*>(h->scalars.as<char>() + 8);
-    p.fail_list = h->fail_list.as<uint32_t>();
-    p.fail_n = reinterpret_cast<uint32_t*>(h->scalars.as<char>() + 4);
-    p.fail_cap = kFailCap;
-    p.job = ji;
     f->n_passes = (int32_t)tps.size();
     f->tbits = j.tbits;
     if (tps.size() <= 2) {   // (one or two passes per lane -- TUMBLE, HOP / CUMULATE flushes: in the
@@ -1541,6 +1547,372 @@ int plan_heavy(fg_handle* h, const StagedBatch* d_sb, int nb, int64_t fill, Heav
     return FG_OK;
 }
 
+// ---- merge jobs: one launch path ---------------------------------------------------------------
+// grid of the compact merge (two workgroups per CU)
+int compact_grid(const fg_handle* h) { return std::min(h->P, 2 * h->merge_grid); }
+
+// One merge as a job: registered for the region retry (job_add), its parameters at the current
+// regions (job_params), the caller's variant of them -- tweak(p, &grid): compact / narrow /
+// fast_stream / hot_keys / heavy, and the grid where it is not merge_grid(h) -- then the launch,
+// timed as the job's class over `records`. *p: the parameters as launched.
+template <class Tweak>
+int run_merge_job(fg_handle* h, MergeJob&& job, int64_t records, MergeParams* p, Tweak tweak) {
+    const int kclass = job.kclass;
+    int ji = 0;
+    if (int rc = job_add(h, std::move(job), &ji)) return rc;
+    if (int rc = job_params(h, ji, p)) return rc;
+    int grid = merge_grid(h);
+    if (int rc = tweak(*p, &grid)) return rc;
+    KTimer kt(h, kclass, records);
+    HIPCHK(h, launch_merge(*p, grid, h->stream));
+    return FG_OK;
+}
+int run_merge_job(fg_handle* h, MergeJob&& job, int64_t records) {   // the general merge as it is
+    MergeParams p{};
+    return run_merge_job(h, std::move(job), records, &p, [](MergeParams&, int*) { return FG_OK; });
+}
+
+// The resident sources of a merge allow the compact merge (32-bit LDS counts, 20-B slots): one
+// value accumulator, no NULL counts, marks or chains, at most 64 of them, COUNT(*)s below 2^32
+bool compact_sources_ok(const fg_handle* h, const MergeParams& p) {
+    return !h->mv && p.src_null_mask == 0 && !p.mark_mask && !p.markonly_mask && !p.emit_marked && p.dst_mode == 0 &&
+           p.n_src <= 64 && ub_cnt_fits(h);
+}
+
+// Room for the at most `ub` rows a fire adds: the fired-row counter zeroed (or re-based) once per
+// advance, the output buffers grown, the rows counted as pending until the fire is collected
+// (`pending`). `zeroed`: the caller's own fill zeroed the counter already (flush_lanes).
+int reserve_fired(fg_handle* h, int64_t ub, bool pending = true, bool zeroed = false) {
+    if (zeroed && !h->out_count_reset && h->adv_base + h->late_rows == 0) h->out_count_reset = true;
+    if (int rc = reset_out_count(h)) return rc;
+    if (int rc = ensure_out(h, h->out_n + h->pending_out + ub)) return rc;
+    if (pending) h->pending_out += ub;
+    return FG_OK;
+}
+
+// After the last launch of a job set: the scalars read back (one synchronization), the regions
+// that overflowed split and redone (settle_jobs), the overflow flags checked. rows_class >= 0: the
+// set fired rows -- the fired-row count taken, the new rows credited to that kernel class.
+int collect_jobs(fg_handle* h, int rows_class) {
+    HIPCHK(h, hipMemcpyAsync(h->h_scalars.p, h->scalars.p, kScalarBytes, hipMemcpyDeviceToHost, h->stream));
+    if (int rc = sync(h)) return rc;
+    if (int rc = settle_jobs(h)) return rc;
+    if (int rc = check_overflow(h)) return rc;
+    if (rows_class >= 0) {
+        const int64_t before = h->out_n;
+        h->out_n = (int64_t)h->h_scalars.as<unsigned long long>()[1];
+        h->kstat[rows_class].rows += h->out_n - before;
+        h->pending_out = 0;
+    }
+    return FG_OK;
+}
+
+// One tile job: lane l's tile passes (busy until the job settles) as the batches of `job`, its
+// TileFire, then the fire -- a workgroup per bucket, timed as the job's class; the split fire
+// (K_TILE_SPLIT) when a pass is skewed or, `may_spread` (the plain tile fire only), when the lane
+// has fewer buckets than CUs (a small key space, configs[0]): ~2 chunk items per CU, where one
+// workgroup per bucket would leave most of the GPU idle.
+int run_tile_job(fg_handle* h, int l, MergeJob&& job, bool may_spread) {
+    const Lane& ln = h->lane[l];
+    bool skewed = false;
+    for (Staged* st : ln.passes) {
+        job.batches.push_back(JobBatch{st, l, StagedBatch{}, 0});
+        st->busy = true;
+        skewed = skewed || st->skew;
+    }
+    job.tile = true;
+    job.tbits = ln.passes[0]->bits;
+    const int kclass = job.kclass;
+    int ji = 0;
+    if (int rc = job_add(h, std::move(job), &ji)) return rc;
+    TileFire f{};
+    if (int rc = tile_job_params(h, ji, &f)) return rc;
+    const int nbk = 1 << (f.tbits - kTileBits);
+    const bool spread = may_spread && h->tile_split && nbk < h->merge_grid && ln.fill >= kTileSpreadMin &&
+                        ln.passes.size() <= (size_t)kMaxTilePasses;
+    KTimer kt(h, skewed || spread ? K_TILE_SPLIT : kclass, ln.fill);
+    if (skewed)
+        return tile_split_fire(h, ln, f, h->tile_chunk);
+    if (spread)
+        return tile_split_fire(h, ln, f, (uint32_t)std::max<int64_t>(kTileSpreadChunk, ln.fill / (2 * h->merge_grid)));
+    HIPCHK(h, tile_fire_launch(h, f, std::min(nbk, h->merge_grid), h->stream));
+    return FG_OK;
+}
+
+// ---- flush_lanes, lane by lane -----------------------------------------------------------------
+struct FlushRun {   // what one flush_lanes call gathers over its lanes
+    bool zeroed_out = false;   // its fill zeroed the fired-row counter too (reserve_fired)
+    std::vector<int64_t> fired_tables, retained;   // slices freed / retired at its end
+    bool any_emit = false;
+    int fire_class = K_FLUSH_FIRE;   // kernel class credited with the fired rows
+};
+struct LanePlan {
+    int l = 0;
+    int64_t se = 0;          // the lane's slice end
+    bool due = false;        // the slice's timer fires in this advance
+    bool fire_now = false;   // the lane's merge emits the slice's window (TUMBLE) or partials (local phase)
+    bool cum_fire = false;   // ... or the CUMULATE step window W = se (plan_lane)
+    // the tables of the lane's merge (plan_lane_tables)
+    SliceTable* t = nullptr;      // the slice's own (null: fired without one)
+    SliceTable* F = nullptr;      // first slice's table of W's cumulative window
+    SliceTable* dstt = nullptr;   // table written by this merge (null: none)
+    std::vector<SliceTable*> srcs;
+    int64_t cum_first = 0, cum_last = 0;   // cum_fire: first and last slice end of W's cumulative window
+    int64_t ub = 0;               // bound on the entries (and rows) of the merge's result
+    bool emit() const { return fire_now || cum_fire; }
+};
+
+LanePlan plan_lane(const fg_handle* h, int l, const FireRange* fire) {
+    LanePlan pl;
+    pl.l = l;
+    pl.se = slice_end_of(h, h->lane[l].q);
+    const int64_t trig = trigger_time(h->w, pl.se);
+    pl.due = fire && pl.se != JMAX && trig > fire->prev && trig <= fire->wm;
+    // local phase: every fired slice lane emits its partial accumulators
+    pl.fire_now = fire && (h->local || (h->w.kind == TUMBLE && pl.due));
+    // CUMULATE: the step window W = se fires now -- combine the staged slice with the
+    // first slice's state, write the state back (unless W is the last window) and emit
+    // W in one pass, instead of a flush into the slice table and a fire re-reading it
+    // (CumulativeSliceAssigner.mergeSlices :359-370 + SliceSharedWindowAggProcessor.fireWindow)
+    // (only when every earlier step window of this cumulative window fired in an earlier
+    // advance, so that no earlier window still has to fire from the unextended state)
+    // (not while a restore re-fire is pending: the re-fire folds the new state of this
+    // cumulative window's earlier slices into its first slice first -- advance_progress runs
+    // it after this flush -- and fire_windows then fires W from the complete state)
+    pl.cum_fire = !h->local && h->w.kind == CUMULATE && pl.due && h->refire_hi == JMIN;
+    if (pl.cum_fire) {
+        const int64_t ws0 = window_start(h->w, pl.se);
+        const int64_t prev_w = jsub(pl.se, h->w.slice);
+        pl.cum_fire = pl.se == jadd(ws0, h->w.slice) || trigger_time(h->w, prev_w) <= fire->prev;
+    }
+    return pl;
+}
+
+// The tables the lane's merge reads and writes (lanes that neither fire straight from the tiles
+// nor belong to a restore re-fire)
+int plan_lane_tables(fg_handle* h, LanePlan& pl) {
+    const Lane& ln = h->lane[pl.l];
+    const int64_t se = pl.se;
+    // a slice fired here whose state is not kept needs no table unless one exists (no fill
+    // of an empty table's counts per fire)
+    if (int rc = table_get(h, se, !(pl.fire_now && !(h->retain && !h->local)), &pl.t)) return rc;
+    pl.dstt = pl.t;
+    if (pl.t && pl.t->upper > 0) pl.srcs.push_back(pl.t);
+    if (pl.cum_fire) {
+        const int64_t ws = window_start(h->w, se);
+        pl.cum_first = jadd(ws, h->w.slice);
+        pl.cum_last = jadd(ws, h->w.size);
+        if (se != pl.cum_first) {
+            if (int rc = table_get(h, pl.cum_first, se != pl.cum_last, &pl.F)) return rc;
+            if (pl.F && pl.F->upper > 0) pl.srcs.push_back(pl.F);
+        }
+        pl.dstt = se == pl.cum_last ? nullptr : (se == pl.cum_first ? pl.t : pl.F);
+    } else if (pl.fire_now) {
+        pl.dstt = h->retain && !h->local ? pl.t : nullptr;   // allowed lateness: the fired window keeps its state
+    }
+    int64_t ub_in = ln.fill + ln.acc_fill;
+    for (SliceTable* r : pl.srcs) ub_in += r->upper;
+    pl.ub = std::min<int64_t>(ub_in, kStateCapMax);
+    return FG_OK;
+}
+
+// the planned merge as a job (its batches: the caller's)
+MergeJob lane_job(LanePlan& pl) {
+    MergeJob job;
+    job.srcs = std::move(pl.srcs);
+    job.dst = pl.dstt;
+    job.emit = pl.emit();
+    job.wend = pl.se;
+    job.kclass = pl.emit() ? K_FLUSH_FIRE : K_FLUSH;
+    return job;
+}
+
+// Outcome 1, the plain tile fire: a TUMBLE window (or a local slice) due now, without resident
+// state, fires straight from the lane's tile passes. *fired false: not this lane.
+int flush_tile_fire(fg_handle* h, FlushRun& fr, const LanePlan& pl, bool* fired) {
+    const Lane& ln = h->lane[pl.l];
+    *fired = false;
+    SliceTable* t0 = nullptr;
+    if (int rc = table_get(h, pl.se, false, &t0)) return rc;
+    if (!(pl.fire_now && !refire_slice(h, pl.se) && !(h->retain && !h->local) && (!t0 || t0->upper == 0) &&
+          tile_fire_ok(h, ln, tile_split_ok(h))))
+        return FG_OK;
+    if (int rc = reserve_fired(h, std::min<int64_t>(ln.fill, kStateCapMax), true, fr.zeroed_out)) return rc;
+    MergeJob job;
+    job.emit = true;
+    job.wend = pl.se;
+    job.kclass = K_TILE_FIRE;
+    if (int rc = run_tile_job(h, pl.l, std::move(job), true)) return rc;
+    if (t0) fr.fired_tables.push_back(pl.se);
+    fr.any_emit = true;
+    fr.fire_class = K_TILE_FIRE;
+    *fired = true;
+    return FG_OK;
+}
+
+// Outcome 2, after a restore: records of a slice whose windows fired before the checkpoint --
+// their state (re_new) and their keys (re_delta, at the window their timer chain
+// starts from: the slice's own, or for a record accepted late the first window not
+// fired at its arrival, AbstractWindowAggProcessor.java:148-156)
+int flush_refire_lane(fg_handle* h, const LanePlan& pl) {
+    const Lane& ln = h->lane[pl.l];
+    SliceTable *T = nullptr, *D = nullptr;
+    if (int rc = side_create(h, h->re_new, pl.se, &T)) return rc;
+    int64_t U = pl.se;
+    while (U != JMAX && trigger_time(h->w, U) <= h->arrival_progress) U = jadd(U, h->w.slice);
+    const bool ds = h->cfg.mode == FG_MODE_DATASTREAM;   // (per-window state: no chains)
+    if (!ds) {
+        if (int rc = side_create(h, h->re_delta, U, &D)) return rc;
+    }
+    for (SliceTable* x : {T, D}) {
+        if (!x) continue;
+        MergeJob job;
+        for (Staged* st : ln.passes) job.batches.push_back(JobBatch{st, pl.l, StagedBatch{}, 0});
+        if (x->upper > 0) job.srcs.push_back(x);
+        job.dst = x;
+        job.kclass = K_FLUSH;
+        if (int rc = run_merge_job(h, std::move(job), ln.fill)) return rc;
+        x->upper = std::min<int64_t>(x->upper + ln.fill + ln.acc_fill, kStateCapMax);
+        x->changed = true;
+    }
+    return FG_OK;
+}
+
+// Outcome 3, the tile fire or tile flush with tables: the lane's tile passes straight into the
+// slice state (and the fired window's rows): the resident tables the merge would read inserted
+// first, the destination's regions written back by the same workgroups -- no materialized pass,
+// no staged pass 2. *done false: the lane does not qualify (the plan is untouched).
+int flush_tile_tables(fg_handle* h, FlushRun& fr, LanePlan& pl, bool* done) {
+    const Lane& ln = h->lane[pl.l];
+    *done = false;
+    // (an item's (source, region) ranges fit the kernel's kTileMaxRegions prefix slots)
+    const int tsub = kTileBits + h->region_bits - ln.passes[0]->bits;
+    bool ok = tile_fire_ok(h, ln, tile_split_ok(h)) && h->keys32 && ub_cnt_fits(h) && pl.srcs.size() <= 8 &&
+              tsub <= kTileMaxRegionBits && ((int64_t)pl.srcs.size() << tsub) <= (int64_t)kTileMaxRegions &&
+              !(pl.emit() && h->retain && !h->local);
+    for (SliceTable* x : pl.srcs) ok = ok && !x->has_null;
+    if (!ok) return FG_OK;
+    MergeJob job = lane_job(pl);
+    // an empty destination takes the 16-B layout (FG_NARROW_TABLES=0: wide, A/B) -- not
+    // for HOP, whose fires read the slice tables through the compact merge: A/B on one box
+    // (profiles/r05/hop_narrow) 0.507 vs 0.445 ms per merge fire reading narrow vs wide
+    // entries, 46.1 vs 44.4 ms per 1B records; CUMULATE's tile fire gains (59.0 vs 62.7)
+#if defined(FG_HOP_WIDE)
+    if (job.dst && job.dst->upper == 0 && h->narrow_tables && !h->mv && h->w.kind != HOP)
+#else
+    if (job.dst && job.dst->upper == 0 && h->narrow_tables && !h->mv)
+#endif
+        job.dst->narrow = true;
+    job.kclass = job.emit ? K_TILE_FIRE : K_TILE_FLUSH;
+    if (job.emit) fr.fire_class = K_TILE_FIRE;
+    // (a skewed pass: the split fire, with the job's tables and h->tile_chunk; never a spread)
+    if (int rc = run_tile_job(h, pl.l, std::move(job), false)) return rc;
+    *done = true;
+    return FG_OK;
+}
+
+// Outcome 4, the general merge of the lane's staged passes, skewed regions by the heavy pass
+int flush_merge_lane(fg_handle* h, LanePlan& pl) {
+    const Lane& ln = h->lane[pl.l];
+    MergeJob job = lane_job(pl);
+    for (Staged* s : ln.passes) job.batches.push_back(JobBatch{s, pl.l, StagedBatch{}, 0});
+    // fast variants: plain staged {key, value} records bucketed at the current regions
+    bool plain = h->st_stride == 2 && !ln.passes.empty() && ln.passes.size() <= (size_t)kMaxMergeBatches;
+    // skewed regions take the chunked heavy pass (passes bucketed at the current regions)
+    bool skew = false, same_bits = true;
+    for (Staged* s : ln.passes) {
+        plain = plain && !s->has_null && !s->is_acc && s->bits == h->region_bits && s->narrow == ln.passes[0]->narrow;
+        skew = skew || s->skew;
+        same_bits = same_bits && s->bits == h->region_bits;
+    }
+    const bool heavy = skew && same_bits;
+    HeavyPlan hp{};
+    Stamps st(h->stream);
+    MergeParams p{};
+    int rc = run_merge_job(h, std::move(job), ln.fill, &p, [&](MergeParams& p, int* grid) {
+        p.fast_stream = plain ? 1 : 0;
+        p.narrow = plain && ln.passes[0]->narrow ? 1 : 0;
+        // compact LDS table (two workgroups per CU) when no resident state is read and the
+        // COUNT(*) of a key cannot reach 2^32
+        // (resident sources: plain ones -- no NULL counts, marks or chains -- at a COUNT(*) bound
+        // below 2^32, keyed by their int32 keys under narrow staging; a fired window that keeps
+        // its state (allowed lateness) takes the wide merge)
+        const bool src_ok = p.n_src == 0 || (compact_sources_ok(h, p) && (!p.narrow || h->keys32));
+        p.compact = plain && src_ok && ln.fill < ((int64_t)1 << 32) && !(p.emit && p.has_dst && h->retain) ? 1 : 0;
+        if (p.compact && !h->mv) *grid = compact_grid(h);
+        p.stamps = st.arm();
+        p.hot_keys = skew ? 1 : 0;
+        if (heavy) {
+            if (int rc = plan_heavy(h, p.batches, p.n_batches, ln.fill + ln.acc_fill, &hp)) return rc;
+            p.heavy = hp.heavy;
+        }
+        return (int)FG_OK;
+    });
+    if (rc) return rc;
+    if (heavy) {
+        // the heavy regions: chunk tables, then their merge with the region's state
+        KTimer kt(h, K_HEAVY, 0);
+        HIPCHK(h, launch_heavy_chunks(hp, h->merge_grid, h->stream));
+        MergeParams q = p;
+        q.compact = 0;
+        q.fast_stream = 0;
+        q.n_batches = 0;
+        q.batches = nullptr;
+        q.heavy = nullptr;
+        q.region_list = hp.region_list;
+        q.n_list = hp.n_list;
+        q.chunk0 = hp.chunk0;
+        q.part_key = hp.part_key;
+        q.part_cs = hp.part_cs;
+        q.part_cn = hp.part_cn;
+        q.part_sum = hp.part_sum;
+        q.part_v1 = hp.part_v1;
+        q.part_v2 = hp.part_v2;
+        q.part_n = hp.part_n;
+        HIPCHK(h, launch_merge(q, merge_grid(h), h->stream));
+    }
+    st.report([&](const unsigned long long* v) {
+        const int waves = (p.compact ? compact_grid(h) * kCompactMergeThreads : merge_grid(h) * kMergeThreads) / 64;
+        fprintf(stderr, "[fg stamps] merge %s P=%d records=%lld: clear %.0f stream %.0f compact %.0f emit %.0f (cycles/wave)\n",
+                p.compact ? "compact" : "wide", h->P, (long long)ln.fill, (double)v[0] / waves,
+                (double)v[1] / waves, (double)v[2] / waves, (double)v[3] / waves);
+    });
+    return FG_OK;
+}
+
+// The host's bookkeeping of a lane whose merge (outcome 3 or 4) is queued: the tables' entry
+// bounds, the slices to free or retire at the end of the flush
+void lane_flushed(fg_handle* h, FlushRun& fr, const LanePlan& pl) {
+    const Lane& ln = h->lane[pl.l];
+    const int64_t se = pl.se;
+    if (pl.fire_now) {
+        if (h->retain && !h->local) {
+            pl.t->upper = pl.ub;
+            pl.t->changed = true;
+            fr.retained.push_back(se);
+        } else if (pl.t) {
+            fr.fired_tables.push_back(se);
+        }
+        fr.any_emit = true;
+    } else if (pl.cum_fire) {
+        fr.any_emit = true;
+        h->fused_fired.insert(se);   // fire_windows must not fire W again
+        if (pl.dstt) {
+            pl.dstt->upper = pl.ub;
+            pl.dstt->changed = true;
+        }
+        if (se == pl.cum_last) {        // the cumulative window is complete
+            fr.fired_tables.push_back(se);
+            if (se != pl.cum_first) fr.fired_tables.push_back(pl.cum_first);
+        } else if (se != pl.cum_first) {
+            fr.fired_tables.push_back(se);   // folded into the first slice
+        }
+    } else {
+        pl.t->upper = std::min<int64_t>(pl.t->upper + ln.fill + ln.acc_fill, kStateCapMax);
+        pl.t->changed = true;
+    }
+}
+
 // RecordsWindowBuffer.flush (:108-119) + AggCombiner.combine (:76-115): merge staged slice
 // lanes into their slice tables -- every lane, or (only_fired) the lanes whose slice is
 // fired at the current progress, the only ones a window firing now can read; the others
@@ -1556,369 +1928,53 @@ int flush_lanes(fg_handle* h, const std::vector<int>& sel_in, const FireRange* f
     std::sort(sel.begin(), sel.end(), [&](int a, int b) { return h->lane[a].q < h->lane[b].q; });
     // flags (and out_count unless this advance already counts rows; and the fail count when no
     // job is pending) zeroed by one fill: reset_out_count and job_add then need none of their own
-    bool zeroed_out = false;
-    if (h->out_count_reset) {
-        if (int rc0 = zero_scalars(h, false)) return rc0;   // keep out_count
-    } else {
-        if (int rc0 = zero_scalars(h, true)) return rc0;
-        zeroed_out = true;
-    }
-    std::vector<int64_t> fired_tables, retained;
-    bool any_emit = false;
-    int fire_class = K_FLUSH_FIRE;   // kernel class credited with the fired rows
+    FlushRun fr;
+    fr.zeroed_out = !h->out_count_reset;
+    if (int rc0 = zero_scalars(h, fr.zeroed_out)) return rc0;   // (out_count kept once the advance counts rows)
     int rc;
     for (int l : sel) {
-        const Lane& ln = h->lane[l];
-        const int64_t se = slice_end_of(h, ln.q);
-        bool lane_tiles = false;
-        for (const Staged* st : ln.passes) lane_tiles = lane_tiles || st->tiles;
-        if (lane_tiles) {
+        LanePlan pl = plan_lane(h, l, fire);
+        bool tiles = false;
+        for (const Staged* st : h->lane[l].passes) tiles = tiles || st->tiles;
+        if (tiles) {
             // tile passes: a TUMBLE window (or a local slice) due now fires straight from the
             // tiles; anything else reads the lane's records once they are materialized
-            const int64_t trig0 = trigger_time(h->w, se);
-            const bool due0 = fire && se != JMAX && trig0 > fire->prev && trig0 <= fire->wm;
-            const bool fire0 = fire && (h->local || (h->w.kind == TUMBLE && due0));
-            SliceTable* t0 = nullptr;
-            rc = table_get(h, se, false, &t0);
-            if (rc) return rc;
-            if (fire0 && !refire_slice(h, se) && !(h->retain && !h->local) && (!t0 || t0->upper == 0) &&
-                tile_fire_ok(h, ln, tile_split_ok(h))) {
-                const int64_t ub = std::min<int64_t>(ln.fill, kStateCapMax);
-                if (zeroed_out && !h->out_count_reset && h->adv_base + h->late_rows == 0) h->out_count_reset = true;
-                rc = reset_out_count(h);
-                if (rc) return rc;
-                rc = ensure_out(h, h->out_n + h->pending_out + ub);
-                if (rc) return rc;
-                h->pending_out += ub;
-                MergeJob job;
-                for (Staged* st : ln.passes) {
-                    job.batches.push_back(JobBatch{st, l, StagedBatch{}, 0});
-                    st->busy = true;
-                }
-                job.emit = true;
-                job.wend = se;
-                job.kclass = K_TILE_FIRE;
-                job.tile = true;
-                job.tbits = ln.passes[0]->bits;
-                int ji = 0;
-                rc = job_add(h, std::move(job), &ji);
-                if (rc) return rc;
-                TileFire f{};
-                rc = tile_job_params(h, ji, &f);
-                if (rc) return rc;
-                bool skewed = false;
-                for (const Staged* st : ln.passes) skewed = skewed || st->skew;
-                // a lane of fewer buckets than CUs (a small key space, configs[0]) is split too, into
-                // ~2 items per CU: one workgroup per bucket would leave most of the GPU idle
-                const int nbk = 1 << (f.tbits - kTileBits);
-                const bool spread = h->tile_split && nbk < h->merge_grid && ln.fill >= kTileSpreadMin &&
-                                    ln.passes.size() <= (size_t)kMaxTilePasses;
-                const uint32_t chunk =
-                    skewed ? h->tile_chunk : (uint32_t)std::max<int64_t>(kTileSpreadChunk, ln.fill / (2 * h->merge_grid));
-                {
-                    KTimer kt(h, skewed || spread ? K_TILE_SPLIT : K_TILE_FIRE, ln.fill);
-                    if (skewed || spread) {
-                        rc = tile_split_fire(h, ln, f, chunk);
-                        if (rc) return rc;
-                    } else {
-                        HIPCHK(h, tile_fire_launch(h, f, std::min(1 << (f.tbits - kTileBits), h->merge_grid), h->stream));
-                    }
-                }
-                if (t0) fired_tables.push_back(se);
-                any_emit = true;
-                fire_class = K_TILE_FIRE;
-                continue;
-            }
-            if (refire_slice(h, se) || !h->tile_state) {
-                rc = materialize_lane(h, l);
-                if (rc) return rc;
-                lane_tiles = false;
+            bool fired = false;
+            if ((rc = flush_tile_fire(h, fr, pl, &fired))) return rc;
+            if (fired) continue;
+            if (refire_slice(h, pl.se) || !h->tile_state) {
+                if ((rc = materialize_lane(h, l))) return rc;
+                tiles = false;
             }
         }
-        if (refire_slice(h, se)) {
-            // after a restore, records of a slice whose windows fired before the checkpoint:
-            // their state (re_new) and their keys (re_delta, at the window their timer chain
-            // starts from: the slice's own, or for a record accepted late the first window not
-            // fired at its arrival, AbstractWindowAggProcessor.java:148-156)
-            SliceTable *T = nullptr, *D = nullptr;
-            rc = side_create(h, h->re_new, se, &T);
-            if (rc) return rc;
-            int64_t U = se;
-            while (U != JMAX && trigger_time(h->w, U) <= h->arrival_progress) U = jadd(U, h->w.slice);
-            const bool ds = h->cfg.mode == FG_MODE_DATASTREAM;   // (per-window state: no chains)
-            if (!ds) {
-                rc = side_create(h, h->re_delta, U, &D);
-                if (rc) return rc;
-            }
-            for (SliceTable* x : {T, D}) {
-                if (!x) continue;
-                MergeJob job;
-                for (Staged* st : ln.passes) job.batches.push_back(JobBatch{st, l, StagedBatch{}, 0});
-                if (x->upper > 0) job.srcs.push_back(x);
-                job.dst = x;
-                job.kclass = K_FLUSH;
-                int ji = 0;
-                rc = job_add(h, std::move(job), &ji);
-                if (rc) return rc;
-                MergeParams p{};
-                rc = job_params(h, ji, &p);
-                if (rc) return rc;
-                KTimer kt(h, K_FLUSH, ln.fill);
-                HIPCHK(h, launch_merge(p, merge_grid(h), h->stream));
-                x->upper = std::min<int64_t>(x->upper + ln.fill + ln.acc_fill, kStateCapMax);
-                x->changed = true;
-            }
+        if (refire_slice(h, pl.se)) {
+            if ((rc = flush_refire_lane(h, pl))) return rc;
             continue;
         }
-        const int64_t trig = trigger_time(h->w, se);
-        const bool due = fire && se != JMAX && trig > fire->prev && trig <= fire->wm;
-        // local phase: every fired slice lane emits its partial accumulators
-        const bool fire_now = fire && (h->local || (h->w.kind == TUMBLE && due));
-        // a slice fired here whose state is not kept needs no table unless one exists (no fill
-        // of an empty table's counts per fire)
-        SliceTable* t = nullptr;
-        rc = table_get(h, se, !(fire_now && !(h->retain && !h->local)), &t);
+        rc = plan_lane_tables(h, pl);
+        if (!rc && pl.emit()) rc = reserve_fired(h, pl.ub, true, fr.zeroed_out);
         if (rc) return rc;
-        // CUMULATE: the step window W = se fires now -- combine the staged slice with the
-        // first slice's state, write the state back (unless W is the last window) and emit
-        // W in one pass, instead of a flush into the slice table and a fire re-reading it
-        // (CumulativeSliceAssigner.mergeSlices :359-370 + SliceSharedWindowAggProcessor.fireWindow)
-        // (only when every earlier step window of this cumulative window fired in an earlier
-        // advance, so that no earlier window still has to fire from the unextended state)
-        // (not while a restore re-fire is pending: the re-fire folds the new state of this
-        // cumulative window's earlier slices into its first slice first -- advance_progress runs
-        // it after this flush -- and fire_windows then fires W from the complete state)
-        bool cum_fire = !h->local && h->w.kind == CUMULATE && due && h->refire_hi == JMIN;
-        if (cum_fire) {
-            const int64_t ws0 = window_start(h->w, se);
-            const int64_t prev_w = jsub(se, h->w.slice);
-            cum_fire = se == jadd(ws0, h->w.slice) || trigger_time(h->w, prev_w) <= fire->prev;
-        }
-        SliceTable* F = nullptr;       // first slice's table of W's cumulative window
-        SliceTable* dstt = t;          // table written by this merge (null: none)
-        MergeJob job;
-        if (t && t->upper > 0) job.srcs.push_back(t);
-        int64_t cum_first = 0, cum_last = 0;
-        if (cum_fire) {
-            const int64_t ws = window_start(h->w, se);
-            cum_first = jadd(ws, h->w.slice);
-            cum_last = jadd(ws, h->w.size);
-            if (se != cum_first) {
-                rc = table_get(h, cum_first, se != cum_last, &F);
-                if (rc) return rc;
-                if (F && F->upper > 0) job.srcs.push_back(F);
-            }
-            dstt = se == cum_last ? nullptr : (se == cum_first ? t : F);
-        } else if (fire_now) {
-            dstt = h->retain && !h->local ? t : nullptr;   // allowed lateness: the fired window keeps its state
-        }
-        int64_t ub_in = ln.fill + ln.acc_fill;
-        for (SliceTable* r : job.srcs) ub_in += r->upper;
-        const int64_t ub = std::min<int64_t>(ub_in, kStateCapMax);
-        if (fire_now || cum_fire) {
-            if (zeroed_out && !h->out_count_reset && h->adv_base + h->late_rows == 0) h->out_count_reset = true;
-            rc = reset_out_count(h);
-            if (rc) return rc;
-            rc = ensure_out(h, h->out_n + h->pending_out + ub);
-            if (rc) return rc;
-            h->pending_out += ub;
-        }
-        job.dst = dstt;
-        job.emit = fire_now || cum_fire;
-        job.wend = se;
-        job.kclass = fire_now || cum_fire ? K_FLUSH_FIRE : K_FLUSH;
-        if (lane_tiles) {
-            // the lane's tile passes straight into the slice state (and the fired window's rows):
-            // the resident tables the merge would read inserted first, the destination's regions
-            // written back by the same workgroups -- no materialized pass, no staged pass 2
-            // (an item's (source, region) ranges fit the kernel's kTileMaxRegions prefix slots)
-            const int tsub = kTileBits + h->region_bits - ln.passes[0]->bits;
-            bool ok = tile_fire_ok(h, ln, tile_split_ok(h)) && h->keys32 && ub_cnt_fits(h) && job.srcs.size() <= 8 &&
-                      tsub <= kTileMaxRegionBits &&
-                      ((int64_t)job.srcs.size() << tsub) <= (int64_t)kTileMaxRegions &&
-                      !(job.emit && h->retain && !h->local);
-            for (SliceTable* x : job.srcs) ok = ok && !x->has_null;
-            if (ok) {
-                for (Staged* st : ln.passes) {
-                    job.batches.push_back(JobBatch{st, l, StagedBatch{}, 0});
-                    st->busy = true;
-                }
-                // an empty destination takes the 16-B layout (FG_NARROW_TABLES=0: wide, A/B) -- not
-                // for HOP, whose fires read the slice tables through the compact merge: A/B on one box
-                // (profiles/r05/hop_narrow) 0.507 vs 0.445 ms per merge fire reading narrow vs wide
-                // entries, 46.1 vs 44.4 ms per 1B records; CUMULATE's tile fire gains (59.0 vs 62.7)
-#if defined(FG_HOP_WIDE)
-                if (job.dst && job.dst->upper == 0 && h->narrow_tables && !h->mv && h->w.kind != HOP)
-#else
-                if (job.dst && job.dst->upper == 0 && h->narrow_tables && !h->mv)
-#endif
-                    job.dst->narrow = true;
-                job.tile = true;
-                job.tbits = ln.passes[0]->bits;
-                job.kclass = job.emit ? K_TILE_FIRE : K_TILE_FLUSH;
-                const int kc = job.kclass;
-                int ji = 0;
-                rc = job_add(h, std::move(job), &ji);
-                if (rc) return rc;
-                TileFire f{};
-                rc = tile_job_params(h, ji, &f);
-                if (rc) return rc;
-                bool skewed = false;   // (a skewed pass: the split fire, with the job's tables)
-                for (const Staged* st : ln.passes) skewed = skewed || st->skew;
-                {
-                    KTimer kt(h, skewed ? K_TILE_SPLIT : kc, ln.fill);
-                    if (skewed) {
-                        rc = tile_split_fire(h, ln, f, h->tile_chunk);
-                        if (rc) return rc;
-                    } else {
-                        HIPCHK(h, tile_fire_launch(h, f, std::min(1 << (f.tbits - kTileBits), h->merge_grid), h->stream));
-                    }
-                }
-                if (kc == K_TILE_FIRE) fire_class = K_TILE_FIRE;
-                goto merged;
-            }
-            rc = materialize_lane(h, l);
+        bool merged = false;
+        if (tiles) {   // straight from the tiles, or materialized for the general merge
+            rc = flush_tile_tables(h, fr, pl, &merged);
+            if (!rc && !merged) rc = materialize_lane(h, l);
             if (rc) return rc;
         }
-        for (Staged* s : ln.passes) job.batches.push_back(JobBatch{s, l, StagedBatch{}, 0});
-        {
-        int ji = 0;
-        rc = job_add(h, std::move(job), &ji);
-        if (rc) return rc;
-        MergeParams p{};
-        rc = job_params(h, ji, &p);
-        if (rc) return rc;
-        // fast variants: plain staged {key, value} records bucketed at the current regions
-        bool plain = h->st_stride == 2 && !ln.passes.empty() && ln.passes.size() <= (size_t)kMaxMergeBatches;
-        for (Staged* s : ln.passes)
-            plain = plain && !s->has_null && !s->is_acc && s->bits == h->region_bits && s->narrow == ln.passes[0]->narrow;
-        p.fast_stream = plain ? 1 : 0;
-        p.narrow = plain && ln.passes[0]->narrow ? 1 : 0;
-        // compact LDS table (two workgroups per CU) when no resident state is read and the
-        // COUNT(*) of a key cannot reach 2^32
-        // (resident sources: plain ones -- no NULL counts, marks or chains -- at a COUNT(*) bound
-        // below 2^32, keyed by their int32 keys under narrow staging; a fired window that keeps
-        // its state (allowed lateness) takes the wide merge)
-        const bool src_ok = p.n_src == 0 ||
-                            (!h->mv && p.src_null_mask == 0 && !p.mark_mask && !p.markonly_mask &&
-                             !p.emit_marked && p.dst_mode == 0 && p.n_src <= 64 && ub_cnt_fits(h) &&
-                             (!p.narrow || h->keys32));
-        p.compact = plain && src_ok && ln.fill < ((int64_t)1 << 32) && !(p.emit && p.has_dst && h->retain) ? 1 : 0;
-#ifdef FG_STAMPS
-        static DevBuf d_st;
-        if (getenv("FG_STAMPS")) {
-            HIPCHK(h, d_st.ensure(64));
-            HIPCHK(h, hipMemsetAsync(d_st.p, 0, 64, h->stream));
-            p.stamps = d_st.as<unsigned long long>();
+        if (!merged) {
+            if ((rc = flush_merge_lane(h, pl))) return rc;
         }
-#endif
-        // skewed regions take the chunked heavy pass (passes bucketed at the current regions)
-        bool skew = false, same_bits = true;
-        for (Staged* s : ln.passes) {
-            skew = skew || s->skew;
-            same_bits = same_bits && s->bits == h->region_bits;
-        }
-        p.hot_keys = skew ? 1 : 0;
-        skew = skew && same_bits;
-        HeavyPlan hp{};
-        if (skew) {
-            rc = plan_heavy(h, p.batches, p.n_batches, ln.fill + ln.acc_fill, &hp);
-            if (rc) return rc;
-            p.heavy = hp.heavy;
-        }
-        {
-            KTimer kt(h, fire_now || cum_fire ? K_FLUSH_FIRE : K_FLUSH, ln.fill);
-            HIPCHK(h, launch_merge(p, p.compact && !h->mv ? std::min(h->P, 2 * h->merge_grid) : merge_grid(h), h->stream));
-        }
-        if (skew) {
-            // the heavy regions: chunk tables, then their merge with the region's state
-            KTimer kt(h, K_HEAVY, 0);
-            HIPCHK(h, launch_heavy_chunks(hp, h->merge_grid, h->stream));
-            MergeParams q = p;
-            q.compact = 0;
-            q.fast_stream = 0;
-            q.n_batches = 0;
-            q.batches = nullptr;
-            q.heavy = nullptr;
-            q.region_list = hp.region_list;
-            q.n_list = hp.n_list;
-            q.chunk0 = hp.chunk0;
-            q.part_key = hp.part_key;
-            q.part_cs = hp.part_cs;
-            q.part_cn = hp.part_cn;
-            q.part_sum = hp.part_sum;
-            q.part_v1 = hp.part_v1;
-            q.part_v2 = hp.part_v2;
-            q.part_n = hp.part_n;
-            HIPCHK(h, launch_merge(q, merge_grid(h), h->stream));
-        }
-#ifdef FG_STAMPS
-        if (p.stamps) {
-            unsigned long long st[4];
-            HIPCHK(h, hipMemcpyAsync(st, d_st.p, 32, hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            const int waves = (p.compact ? std::min(h->P, 2 * h->merge_grid) * kCompactMergeThreads
-                                         : merge_grid(h) * kMergeThreads) / 64;
-            fprintf(stderr, "[fg stamps] merge %s P=%d records=%lld: clear %.0f stream %.0f compact %.0f emit %.0f (cycles/wave)\n",
-                    p.compact ? "compact" : "wide", h->P, (long long)ln.fill, (double)st[0] / waves,
-                    (double)st[1] / waves, (double)st[2] / waves, (double)st[3] / waves);
-        }
-#endif
-        }
-    merged:
-        if (fire_now) {
-            if (h->retain && !h->local) {
-                t->upper = ub;
-                t->changed = true;
-                retained.push_back(se);
-            } else if (t) {
-                fired_tables.push_back(se);
-            }
-            any_emit = true;
-        } else if (cum_fire) {
-            any_emit = true;
-            h->fused_fired.insert(se);   // fire_windows must not fire W again
-            if (dstt) {
-                dstt->upper = ub;
-                dstt->changed = true;
-            }
-            if (se == cum_last) {        // the cumulative window is complete
-                fired_tables.push_back(se);
-                if (se != cum_first) fired_tables.push_back(cum_first);
-            } else if (se != cum_first) {
-                fired_tables.push_back(se);   // folded into the first slice
-            }
-        } else {
-            t->upper = std::min<int64_t>(t->upper + ln.fill + ln.acc_fill, kStateCapMax);
-            t->changed = true;
-        }
+        lane_flushed(h, fr, pl);
     }
-    if (h->async_advance && any_emit) {
+    if (h->async_advance && fr.any_emit) {
         // fg_advance_progress_async: the host's bookkeeping now, the device's results later
-        // (complete_fire); tables freed here are held until then
-        rc = publish_fire(h, fire_class);   // (first: the tables freed below are held)
-        if (rc) return rc;
-        for (int64_t se : fired_tables) table_free(h, se);
-        for (int64_t se : retained) retire(h, se, se);
-        for (int l : sel) release_lane(h, l);
-        h->flushes++;
-        return FG_OK;
+        // (complete_fire); tables freed here are held until then (so: published first)
+        rc = publish_fire(h, fr.fire_class);
+    } else {
+        rc = collect_jobs(h, fr.any_emit ? fr.fire_class : -1);   // (regions that overflowed: split and redone)
     }
-    HIPCHK(h, hipMemcpyAsync(h->h_scalars.p, h->scalars.p, kScalarBytes, hipMemcpyDeviceToHost, h->stream));
-    rc = sync(h);
     if (rc) return rc;
-    rc = settle_jobs(h);   // regions that overflowed: split and redone
-    if (rc) return rc;
-    rc = check_overflow(h);
-    if (rc) return rc;
-    if (any_emit) {
-        const int64_t before = h->out_n;
-        h->out_n = (int64_t)h->h_scalars.as<unsigned long long>()[1];
-        h->kstat[fire_class].rows += h->out_n - before;
-        h->pending_out = 0;
-    }
-    for (int64_t se : fired_tables) table_free(h, se);
-    for (int64_t se : retained) retire(h, se, se);
+    for (int64_t se : fr.fired_tables) table_free(h, se);
+    for (int64_t se : fr.retained) retire(h, se, se);
     for (int l : sel) release_lane(h, l);
     h->flushes++;
     return FG_OK;
@@ -1960,9 +2016,8 @@ int fire_one(fg_handle* h, int64_t wend, const std::vector<SliceTable*>& srcs, S
     for (auto* s : srcs) ub += s->upper;
     ub = std::min<int64_t>(ub, kStateCapMax);
     if (ub == 0 && dst == nullptr) return FG_OK;
-    int rc = reset_out_count(h);
-    if (rc) return rc;
-    rc = ensure_out(h, h->out_n + h->pending_out + ub);
+    // (rows pending only when deferred: under async_advance fire_collect does not zero pending_out)
+    int rc = reserve_fired(h, ub, defer);
     if (rc) return rc;
     if (srcs.size() == 1 && !dst) {   // one table, nothing written: rows straight from it (cannot overflow)
         MergeParams p{};
@@ -1980,54 +2035,31 @@ int fire_one(fg_handle* h, int64_t wend, const std::vector<SliceTable*>& srcs, S
         j.emit = true;
         j.wend = wend;
         j.kclass = K_FIRE;
-        int ji = 0;
-        rc = job_add(h, std::move(j), &ji);
-        if (rc) return rc;
+        Stamps st(h->stream);
         MergeParams p{};
-        rc = job_params(h, ji, &p);
+        rc = run_merge_job(h, std::move(j), 0, &p, [&](MergeParams& p, int* grid) {
+            p.stamps = st.arm();
+            // the compact merge (two workgroups per CU, 20-B LDS slots) when the window is plain
+            // resident state: source tables without NULL counts or marks, nothing written back, one
+            // value accumulator, COUNT(*)s below 2^32
+            p.compact = !dst && p.n_batches == 0 && compact_sources_ok(h, p) ? 1 : 0;
+            p.narrow = p.compact && h->keys32 ? 1 : 0;   // (narrow LDS table: keys from the entries' mixes)
+            if (p.compact) *grid = compact_grid(h);
+            return FG_OK;
+        });
         if (rc) return rc;
-#ifdef FG_STAMPS
-        static DevBuf d_fst;
-        if (getenv("FG_STAMPS")) {
-            HIPCHK(h, d_fst.ensure(64));
-            HIPCHK(h, hipMemsetAsync(d_fst.p, 0, 64, h->stream));
-            p.stamps = d_fst.as<unsigned long long>();
-        }
-#endif
-        // the compact merge (two workgroups per CU, 20-B LDS slots) when the window is plain
-        // resident state: source tables without NULL counts or marks, nothing written back, one
-        // value accumulator, COUNT(*)s below 2^32
-        p.compact = !h->mv && !dst && p.n_batches == 0 && p.src_null_mask == 0 && !p.mark_mask &&
-                            !p.markonly_mask && !p.emit_marked && p.dst_mode == 0 && p.n_src <= 64 &&
-                            ub_cnt_fits(h)
-                        ? 1
-                        : 0;
-        p.narrow = p.compact && h->keys32 ? 1 : 0;   // (narrow LDS table: keys from the entries' mixes)
-        {
-            KTimer kt(h, K_FIRE, 0);
-            HIPCHK(h, launch_merge(p, p.compact ? std::min(h->P, 2 * h->merge_grid) : merge_grid(h), h->stream));
-        }
-#ifdef FG_STAMPS
-        if (p.stamps) {
-            unsigned long long st[4];
-            HIPCHK(h, hipMemcpyAsync(st, d_fst.p, 32, hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(h, hipStreamSynchronize(h->stream));
+        st.report([&](const unsigned long long* v) {
             const int waves = merge_grid(h) * kMergeThreads / 64;
             fprintf(stderr, "[fg stamps] fire srcs=%zu dst=%d: clear %.0f stream %.0f compact %.0f emit %.0f (cycles/wave)\n",
-                    srcs.size(), dst ? 1 : 0, (double)st[0] / waves, (double)st[1] / waves, (double)st[2] / waves,
-                    (double)st[3] / waves);
-        }
-#endif
+                    srcs.size(), dst ? 1 : 0, (double)v[0] / waves, (double)v[1] / waves, (double)v[2] / waves,
+                    (double)v[3] / waves);
+        });
     }
     if (dst) {
         dst->upper = ub;
         dst->changed = true;
     }
-    if (defer) {
-        h->pending_out += ub;
-        return FG_OK;
-    }
-    return fire_collect(h);
+    return defer ? FG_OK : fire_collect(h);
 }
 
 // after fires: region retries, overflow check and the fired-row count (one synchronization)
@@ -2035,18 +2067,7 @@ int fire_collect(fg_handle* h) {
     if (h->async_advance) {   // fg_advance_progress_async: completed by the next call that needs it
         return publish_fire(h, K_FIRE);   // (tables freed by the fires stay held until then)
     }
-    HIPCHK(h, hipMemcpyAsync(h->h_scalars.p, h->scalars.p, kScalarBytes, hipMemcpyDeviceToHost, h->stream));
-    int rc = sync(h);
-    if (rc) return rc;
-    rc = settle_jobs(h);
-    if (rc) return rc;
-    rc = check_overflow(h);
-    if (rc) return rc;
-    const int64_t before = h->out_n;
-    h->out_n = (int64_t)h->h_scalars.as<unsigned long long>()[1];
-    h->kstat[K_FIRE].rows += h->out_n - before;
-    h->pending_out = 0;
-    return FG_OK;
+    return collect_jobs(h, K_FIRE);
 }
 
 // Fire every window whose timer time lies in (prev, wm] (InternalTimerServiceImpl.advanceWatermark
@@ -2201,12 +2222,8 @@ int refire_job(fg_handle* h, const std::vector<SliceTable*>& vals, const std::ve
     int rc;
     if (emit) {
         if (j.mark_mask == 0) return FG_OK;
-        rc = reset_out_count(h);
+        rc = reserve_fired(h, std::min<int64_t>(ub, kStateCapMax));
         if (rc) return rc;
-        ub = std::min<int64_t>(ub, kStateCapMax);
-        rc = ensure_out(h, h->out_n + h->pending_out + ub);
-        if (rc) return rc;
-        h->pending_out += ub;
         j.emit = true;
         j.emit_marked = 1;
         j.wend = wend;
@@ -2214,15 +2231,9 @@ int refire_job(fg_handle* h, const std::vector<SliceTable*>& vals, const std::ve
     j.dst = dst;
     j.dst_mode = dst_mode;
     j.kclass = K_FIRE;
-    int ji = 0;
-    rc = job_add(h, std::move(j), &ji);
+    rc = run_merge_job(h, std::move(j), 0);
     if (rc) return rc;
-    MergeParams p{};
-    rc = job_params(h, ji, &p);
-    if (rc) return rc;
-    KTimer kt(h, K_FIRE, 0);
-    HIPCHK(h, launch_merge(p, merge_grid(h), h->stream));
-    if (dst) {
+    if (dst) {   // (the sources: the job's, now in h->jobs)
         int64_t u = 0;
         for (SliceTable* t : h->jobs.back().srcs) u += t->upper;
         dst->upper = std::min<int64_t>(u, kStateCapMax);
@@ -5203,22 +5214,9 @@ static int restore_merge_slice(fg_handle* h, int64_t slice_end, const StagedBatc
     j.dst = t;
     j.kclass = K_RESTORE;
     if (int rc0 = zero_scalars(h, true)) return rc0;
-    int ji = 0;
-    rc = job_add(h, std::move(j), &ji);
+    rc = run_merge_job(h, std::move(j), m);
     if (rc) return rc;
-    MergeParams mp{};
-    rc = job_params(h, ji, &mp);
-    if (rc) return rc;
-    {
-        KTimer kt(h, K_RESTORE, m);
-        HIPCHK(h, launch_merge(mp, merge_grid(h), h->stream));
-    }
-    HIPCHK(h, hipMemcpyAsync(h->h_scalars.p, h->scalars.p, kScalarBytes, hipMemcpyDeviceToHost, h->stream));
-    rc = sync(h);
-    if (rc) return rc;
-    rc = settle_jobs(h);
-    if (rc) return rc;
-    rc = check_overflow(h);
+    rc = collect_jobs(h, -1);
     if (rc) return rc;
     t->upper = std::min<int64_t>(t->upper + m, kStateCapMax);
     t->changed = true;
