@@ -104,6 +104,11 @@ class FgRowRuns(C.Structure):
                 ("first_row", C.c_void_p), ("rows", C.c_void_p)]
 
 
+class FgPackedRows(C.Structure):
+    _fields_ = [("n", C.c_int64), ("location", C.c_int32), ("arity", C.c_int32), ("stride", C.c_int32),
+                ("flags", C.c_int32), ("rows", C.c_void_p), ("key", C.c_void_p)]
+
+
 class FgLateRecords(C.Structure):
     _fields_ = [("n", C.c_int64), ("location", C.c_int32), ("reserved0", C.c_int32), ("key", C.c_void_p),
                 ("rowtime", C.c_void_p), ("val", C.c_void_p), ("val_null", C.c_void_p)]
@@ -136,6 +141,7 @@ FLAG_WINDOWED = 8
 FLAG_PURGING_TRIGGER = 16
 BATCH_KEY32, BATCH_ROWTIME32, BATCH_VAL32 = 1, 2, 4   # fg_batch.format
 TOPN_MAX = 1024   # FG_TOPN_MAX
+PACK_KEY_FIELD = 1   # fg_pack_flags
 
 # every symbol include/flinkgpu.h declares
 EXPORTS = (
@@ -148,6 +154,7 @@ EXPORTS = (
     "fg_set_fired_runs", "fg_fired_runs",
     "fg_set_late_output", "fg_collect_late",
     "fg_set_fired_topn",
+    "fg_fired_packed",
     "fg_stream",
     "fg_last_error", "fg_close", "fg_key_groups", "fg_partition_by_owner", "fg_partition_columns_by_owner",
     "fg_abi_version", "fg_key_dict_open", "fg_key_dict_intern", "fg_key_dict_intern_async",
@@ -290,6 +297,9 @@ def load():
     if hasattr(L, "fg_set_fired_topn"):   # (the same)
         L.fg_set_fired_topn.argtypes = [P, C.c_int32, C.c_int32, C.c_int32]
         L.fg_set_fired_topn.restype = C.c_int
+    if hasattr(L, "fg_fired_packed"):   # (the same)
+        L.fg_fired_packed.argtypes = [P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.POINTER(FgPackedRows)]
+        L.fg_fired_packed.restype = C.c_int
     if hasattr(L, "fg_key_dict_retain"):   # (the same)
         L.fg_key_dict_get_stats.argtypes = [P, C.POINTER(FgKeyDictStats)]
         L.fg_key_dict_retain.argtypes = [P, C.c_int32, C.c_int32, C.POINTER(P), C.POINTER(C.c_int64),

@@ -175,13 +175,13 @@ constexpr int64_t kHeavyChunk = 1 << 16;
 
 enum KClass { K_COUNT = 0, K_SCAN, K_SCATTER, K_PART1, K_PART2, K_FLUSH, K_FLUSH_FIRE, K_FIRE, K_EXPORT, K_RESTORE,
               K_HEAVY, K_TILE1, K_TILE_FIRE, K_TILE_MAT, K_TILE_FLUSH, K_TILE_SPLIT, K_RR_FILTER, K_RR_SCATTER,
-              K_EXPORT_GROUP, K_EXPORT_SELECT, K_LATE_OUT, K_TOPN, K_NCLASS };
+              K_EXPORT_GROUP, K_EXPORT_SELECT, K_LATE_OUT, K_TOPN, K_PACK, K_NCLASS };
 const char* const kClassName[K_NCLASS] = {"ingest_count", "ingest_scan",      "ingest_scatter", "ingest_part1",
                                            "ingest_part2", "merge_flush",      "merge_flush_fire", "merge_fire",
                                            "export",       "restore",          "merge_heavy",      "tile_part1",
                                            "tile_fire",    "tile_materialize", "tile_flush",       "tile_split_fire",
                                            "restore_filter", "restore_scatter", "export_group",   "export_select",
-                                           "late_out",       "topn"};
+                                           "late_out",       "topn",            "pack_rows"};
 struct KStat {
     int64_t launches = 0;
     double ms = 0;
@@ -355,6 +355,14 @@ struct fg_handle {
         bool plan_valid = false;
         int64_t plan_wm = 0;
         SliceList plan;
+        // the fired rows are still the ones the last returning call handed back (fg_fired_packed):
+        // set by fg_advance_progress / fg_collect_fired[_to], cleared wherever plan_valid is, except
+        // by fg_fired_runs
+        bool fired_valid = false;
+        void invalidate() {
+            plan_valid = false;
+            fired_valid = false;
+        }
     } snap;
     // key-grouped images: the second column set the export's rows are scattered into (the D2H
     // source), the (slice, key group) counters and offsets
@@ -514,6 +522,11 @@ struct fg_handle {
     DevBuf tp_desc, tp_err;
     DevBuf tp_list[2][4];       // candidate and merged lists: value words, key words, rows, counts
     HostBuf tp_h_desc, tp_h_err;
+    // Packed rows (fg_fired_packed, fg_pack.hip): the rows of the last range asked for, its key column
+    // on the host, the run directory {first_row, window_start, window_end} as the kernel reads it
+    bool pk_listed = false;     // the handle has packed rows: fg_kernel_stats lists the class pack_rows
+    DevBuf pk_rows, pk_runs;
+    HostBuf pk_h_rows, pk_h_key, pk_h_runs;
 
     // stats
     int64_t records_in = 0, rows_fired = 0, flushes = 0;
@@ -595,8 +608,9 @@ struct KTimer {
     int64_t records;
     hipEvent_t a = nullptr, b = nullptr;
     KTimer(fg_handle* hh, int c, int64_t r) : h(hh), cls(c), records(r) {
-        // (the mask's bit i is entry i of fg_kernel_stats' list: topn moves up where late_out is not listed)
-        const int bit = cls == K_TOPN && !h->lo_listed ? cls - 1 : cls;
+        // (the mask's bit i is entry i of fg_kernel_stats' list: topn moves up where late_out is not
+        // listed, pack_rows past either that is not)
+        const int bit = cls - (cls >= K_TOPN && !h->lo_listed ? 1 : 0) - (cls == K_PACK && !h->tp_listed ? 1 : 0);
         if (h->timing && ((h->timing_mask >> bit) & 1u)) {
             a = ev_get(h);
             b = ev_get(h);
@@ -4017,7 +4031,7 @@ int fg_open(const fg_config* cfg, fg_handle** out) {
 
 int fg_add_batch(fg_handle* h, const fg_batch* b) {
     if (!h || !b) return FG_EINVAL;
-    h->snap.plan_valid = false;
+    h->snap.invalidate();
     if (b->n <= 0) return FG_OK;
     if (b->n > (int64_t)0x7fffffff) return h->fail(FG_EINVAL, "batch larger than 2^31-1 records");
     if (!b->key || !b->rowtime) return h->fail(FG_EINVAL, "batch key/rowtime columns are required");
@@ -4188,7 +4202,7 @@ int fg_add_batch(fg_handle* h, const fg_batch* b) {
 
 int fg_add_rows(fg_handle* h, const fg_row_batch* b) {
     if (!h || !b) return FG_EINVAL;
-    h->snap.plan_valid = false;
+    h->snap.invalidate();
     if (b->n <= 0) return FG_OK;
     if (b->n > (int64_t)0x7fffffff) return h->fail(FG_EINVAL, "batch larger than 2^31-1 rows");
     if (!b->rows) return h->fail(FG_EINVAL, "rows pointer is required");
@@ -4263,7 +4277,7 @@ static int add_partials(fg_handle* h, const fg_partials* b) {
     if (h) {
         h->cnt_bound = JMAX;
         h->keys32 = false;
-        h->snap.plan_valid = false;
+        h->snap.invalidate();
     }
     if (!h || !b) return FG_EINVAL;
     if (b->n <= 0) return FG_OK;
@@ -4333,7 +4347,7 @@ static int add_partials(fg_handle* h, const fg_partials* b) {
 
 int fg_flush(fg_handle* h) {
     if (!h) return FG_EINVAL;
-    h->snap.plan_valid = false;
+    h->snap.invalidate();
     HIPCHK(h, hipSetDevice(h->device));
     if (int rc0 = settle_pending(h)) return rc0;
     return flush(h);
@@ -4500,7 +4514,7 @@ static void quiet_progress(fg_handle* h, int64_t wm) {   // advance()'s bookkeep
 
 int fg_advance_progress_async(fg_handle* h, int64_t wm) {
     if (!h) return FG_EINVAL;
-    h->snap.plan_valid = false;
+    h->snap.invalidate();
     HIPCHK(h, hipSetDevice(h->device));
     if (quiet_advance(h, wm)) {
         quiet_progress(h, wm);
@@ -4524,7 +4538,7 @@ int fg_advance_progress_async(fg_handle* h, int64_t wm) {
 
 int fg_advance_progress_async_n(fg_handle* h, const int64_t* wms, int64_t n) {
     if (!h || n < 0 || (n > 0 && !wms)) return FG_EINVAL;
-    h->snap.plan_valid = false;
+    h->snap.invalidate();
     for (int64_t i = 0; i < n; i++)
         if (int rc = fg_advance_progress_async(h, wms[i])) return rc;
     return FG_OK;
@@ -4546,7 +4560,7 @@ static void device_rows(fg_handle* h, int32_t out_location, fg_rows* fired) {
 
 int fg_collect_fired_to(fg_handle* h, int32_t out_location, fg_rows* fired) {
     if (!h || !fired || (out_location != FG_HOST && out_location != FG_DEVICE)) return FG_EINVAL;
-    h->snap.plan_valid = false;
+    h->snap.invalidate();
     HIPCHK(h, hipSetDevice(h->device));
     if (int rc = complete_fire(h)) return rc;
     if (!h->async_open) {   // (every async advance since the last collect fired nothing)
@@ -4561,9 +4575,11 @@ int fg_collect_fired_to(fg_handle* h, int32_t out_location, fg_rows* fired) {
         fired->n = h->out_n;
         fired->num_aggs = h->cfg.num_aggs;
         fired->location = FG_HOST;
-        return copy_out_to_host(h, fired);
+        if (int rc = copy_out_to_host(h, fired)) return rc;
+    } else {
+        device_rows(h, FG_DEVICE, fired);
     }
-    device_rows(h, FG_DEVICE, fired);
+    h->snap.fired_valid = true;
     return FG_OK;
 }
 
@@ -4571,7 +4587,7 @@ int fg_collect_fired(fg_handle* h, fg_rows* fired) { return fg_collect_fired_to(
 
 int fg_flush_partials(fg_handle* h, int32_t out_location, fg_rows* fired) {
     if (!h || !fired || (out_location != FG_HOST && out_location != FG_DEVICE)) return FG_EINVAL;
-    h->snap.plan_valid = false;
+    h->snap.invalidate();
     if (!h->local) return h->fail(FG_ESTATE, "fg_flush_partials on an operator without FG_FLAG_LOCAL_PARTIALS");
     HIPCHK(h, hipSetDevice(h->device));
     h->local_emit_all = true;
@@ -4591,7 +4607,7 @@ int fg_flush_partials(fg_handle* h, int32_t out_location, fg_rows* fired) {
 
 int fg_advance_progress(fg_handle* h, int64_t wm, int32_t out_location, fg_rows* fired) {
     if (!h) return FG_EINVAL;
-    h->snap.plan_valid = false;
+    h->snap.invalidate();
     HIPCHK(h, hipSetDevice(h->device));
     int rc = advance_progress(h, wm);   // (uncollected async rows lead its rows: adv_base)
     if (rc) return rc;
@@ -4613,6 +4629,7 @@ int fg_advance_progress(fg_handle* h, int64_t wm, int32_t out_location, fg_rows*
             device_rows(h, out_location, fired);
         }
     }
+    h->snap.fired_valid = true;
     return FG_OK;
 }
 
@@ -4810,7 +4827,7 @@ static int snapshot_export(fg_handle* h, const char* fn, const uint8_t* want) {
     }
     if (total >= ((int64_t)1 << 32)) return h->fail(FG_EINVAL, "%s: 2^32 or more rows in one image", fn);
     if (nsel > 65535) return h->fail(FG_EINVAL, "%s: more than 65535 slices in one image", fn);
-    s.plan_valid = false;   // consumed
+    s.invalidate();   // consumed
     const size_t P = (size_t)h->P;
     // the tables' region offsets, then their descriptors, in one buffer and one host-to-device copy
     // (with a second small copy the barrier was measured slower: DESIGN.md 7d, "One export path")
@@ -4896,7 +4913,7 @@ static int snapshot_end(fg_handle* h, fg_state_rows* out, int64_t* timer_waterma
 
 int fg_set_snapshot_grouping(fg_handle* h, int32_t key_hash) {
     if (!h) return FG_EINVAL;
-    h->snap.plan_valid = false;
+    h->snap.invalidate();
     if (key_hash >= 0 && key_hash != FG_KEYHASH_BINARYROW_BIGINT && key_hash != FG_KEYHASH_JAVA_LONG &&
         key_hash != FG_KEYHASH_DICT_ID)
         return h->fail(FG_EINVAL, "fg_set_snapshot_grouping: unknown key_hash %d", key_hash);
@@ -4910,7 +4927,7 @@ int fg_set_snapshot_grouping(fg_handle* h, int32_t key_hash) {
 
 int fg_set_fired_runs(fg_handle* h, int32_t on) {
     if (!h) return FG_EINVAL;
-    h->snap.plan_valid = false;
+    h->snap.invalidate();
     const bool want = on != 0;
     if (want && h->local)
         return h->fail(FG_EINVAL, "fg_set_fired_runs: a FG_FLAG_LOCAL_PARTIALS handle's rows feed the exchange, which reads "
@@ -4945,7 +4962,7 @@ int fg_set_fired_runs(fg_handle* h, int32_t on) {
 
 int fg_set_fired_topn(fg_handle* h, int32_t n, int32_t agg_index, int32_t descending) {
     if (!h) return FG_EINVAL;
-    h->snap.plan_valid = false;
+    h->snap.invalidate();
     if (n < 0 || n > FG_TOPN_MAX) return h->fail(FG_EINVAL, "fg_set_fired_topn: n = %d is not in 0 .. %d", n, FG_TOPN_MAX);
     if (n > 0) {
         if (agg_index < 0 || agg_index >= h->cfg.num_aggs)
@@ -4973,7 +4990,7 @@ int fg_set_fired_topn(fg_handle* h, int32_t n, int32_t agg_index, int32_t descen
 
 int fg_fired_runs(fg_handle* h, fg_row_runs* out) {
     if (!h || !out) return FG_EINVAL;
-    h->snap.plan_valid = false;
+    h->snap.plan_valid = false;   // (the fired rows stay the call's: fg_fired_packed)
     if (!h->fired_runs) return h->fail(FG_ESTATE, "fg_fired_runs: run mode is off (fg_set_fired_runs)");
     out->n = (int64_t)h->rd_we.size();
     out->window_start = h->rd_ws.data();
@@ -4984,9 +5001,111 @@ int fg_fired_runs(fg_handle* h, fg_row_runs* out) {
     return FG_OK;
 }
 
+// fg_fired_packed: rows [first_row, first_row + n) of the columns the last returning call handed
+// back (fired_cols: with Top-N the selected rows) as packed BinaryRowData rows -- one launch_pack_rows
+// on the handle's stream, then (FG_HOST) one copy of the rows and one of the key column's range.
+int fg_fired_packed(fg_handle* h, int64_t first_row, int64_t max_rows, int32_t flags, int32_t out_location,
+                    fg_packed_rows* out) {
+    if (!h || !out) return FG_EINVAL;
+    const bool was_valid = h->snap.fired_valid;
+    h->snap.plan_valid = false;   // (the fired rows stay the call's)
+    if (out_location != FG_HOST && out_location != FG_DEVICE)
+        return h->fail(FG_EINVAL, "fg_fired_packed: unknown location %d", out_location);
+    if (flags & ~(int32_t)FG_PACK_KEY_FIELD) return h->fail(FG_EINVAL, "fg_fired_packed: unknown flag bits 0x%x", flags);
+    if (h->cfg.mode == FG_MODE_DATASTREAM)
+        return h->fail(FG_EINVAL, "fg_fired_packed: a FG_MODE_DATASTREAM handle's elements are tuples, not RowData");
+    if (h->local)
+        return h->fail(FG_EINVAL, "fg_fired_packed: a FG_FLAG_LOCAL_PARTIALS handle's rows are accumulator rows, which "
+                                  "have another layout");
+    if (first_row < 0 || max_rows < 0)
+        return h->fail(FG_EINVAL, "fg_fired_packed: first_row = %lld, max_rows = %lld", (long long)first_row,
+                       (long long)max_rows);
+    if (h->fire_pending) return h->fail(FG_ESTATE, "fg_fired_packed: a fire is pending (fg_collect_fired first)");
+    if (h->async_open) return h->fail(FG_ESTATE, "fg_fired_packed: fired rows are not collected yet (fg_collect_fired first)");
+    if (!was_valid)
+        return h->fail(FG_ESTATE, "fg_fired_packed: the fired rows are no longer the ones the last fg_advance_progress / "
+                                  "fg_collect_fired handed back (or no such call was made)");
+    const FiredCols c = fired_cols(h);
+    if (first_row > c.n)
+        return h->fail(FG_EINVAL, "fg_fired_packed: first_row = %lld, the call returned %lld rows", (long long)first_row,
+                       (long long)c.n);
+    const int64_t n = std::min(max_rows, c.n - first_row);
+    const bool kf = (flags & FG_PACK_KEY_FIELD) != 0, host = out_location == FG_HOST;
+    const int32_t arity = h->cfg.num_aggs + 2 + (kf ? 1 : 0), stride = 8 * (arity + 1);
+    if (host && n * stride >= ((int64_t)1 << 31))
+        return h->fail(FG_EINVAL, "fg_fired_packed: %lld rows of %d bytes do not fit a buffer below 2^31 bytes (ask for a "
+                                  "smaller range)", (long long)n, stride);
+    std::memset(out, 0, sizeof *out);
+    out->n = n;
+    out->location = out_location;
+    out->arity = arity;
+    out->stride = stride;
+    out->flags = flags;
+    if (n == 0) return FG_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t bytes = (size_t)n * (size_t)stride;
+    HIPCHK(h, h->pk_rows.ensure(bytes));
+    if (host) {
+        HIPCHK(h, h->pk_h_rows.ensure(bytes));
+        if (!kf) HIPCHK(h, h->pk_h_key.ensure(8 * (size_t)n));
+    }
+    PackRows p{};
+    p.first = first_row;
+    p.n = n;
+    p.num_aggs = h->cfg.num_aggs;
+    p.key_field = kf ? 1 : 0;
+    p.key = c.key->as<int64_t>();
+    p.null_mask = c.null->as<uint8_t>();
+    for (int a = 0; a < h->cfg.num_aggs; a++) p.agg[a] = c.agg[a].as<int64_t>();
+    p.rows = h->pk_rows.as<unsigned long long>();
+    if (h->fired_runs) {   // the directory of the call's rows: {first_row, window_start, window_end}, one upload
+        const size_t R = h->rd_first.size();
+        if (R == 0 || h->rd_first[0] != 0 || h->rd_first.back() + h->rd_rows.back() != c.n)
+            return h->fail(FG_EDEVICE, "internal: fg_fired_packed: the run directory does not cover the call's %lld rows",
+                           (long long)c.n);
+        HIPCHK(h, h->pk_h_runs.ensure(24 * R));
+        HIPCHK(h, h->pk_runs.ensure(24 * R));
+        int64_t* hr = h->pk_h_runs.as<int64_t>();
+        std::memcpy(hr, h->rd_first.data(), 8 * R);
+        std::memcpy(hr + R, h->rd_ws.data(), 8 * R);
+        std::memcpy(hr + 2 * R, h->rd_we.data(), 8 * R);
+        HIPCHK(h, hipMemcpyAsync(h->pk_runs.p, hr, 24 * R, hipMemcpyHostToDevice, h->stream));
+        p.n_runs = (int32_t)R;
+        p.run_first = h->pk_runs.as<int64_t>();
+        p.run_ws = p.run_first + R;
+        p.run_we = p.run_first + 2 * R;
+    } else {
+        p.ws = c.ws->as<int64_t>();
+        p.we = c.we->as<int64_t>();
+    }
+    h->pk_listed = true;
+    {
+        KTimer kt(h, K_PACK, n);
+        HIPCHK(h, launch_pack_rows(p, h->stream));
+    }
+    h->kstat[K_PACK].rows += n;
+    if (host) {
+        HIPCHK(h, hipMemcpyAsync(h->pk_h_rows.p, h->pk_rows.p, bytes, hipMemcpyDeviceToHost, h->stream));
+        if (!kf)
+            HIPCHK(h, hipMemcpyAsync(h->pk_h_key.p, c.key->as<int64_t>() + first_row, 8 * (size_t)n, hipMemcpyDeviceToHost,
+                                     h->stream));
+        // (the run directory's pinned mirror is written again by the next call: that one waits here too)
+        if (int rc = sync(h)) return rc;
+        out->rows = h->pk_h_rows.as<uint8_t>();
+        out->key = kf ? nullptr : h->pk_h_key.as<int64_t>();
+    } else {
+        // (pk_h_runs is read by the queued upload: the next call's memcpy into it must follow it)
+        if (h->fired_runs)
+            if (int rc = sync(h)) return rc;
+        out->rows = h->pk_rows.as<uint8_t>();
+        out->key = kf ? nullptr : c.key->as<int64_t>() + first_row;
+    }
+    return FG_OK;
+}
+
 int fg_set_late_output(fg_handle* h, int32_t on) {
     if (!h) return FG_EINVAL;
-    h->snap.plan_valid = false;
+    h->snap.invalidate();
     const bool want = on != 0;
     if (want && (h->cfg.mode != FG_MODE_DATASTREAM || h->local || h->proctime || h->windowed))
         return h->fail(FG_EINVAL, "fg_set_late_output: sideOutputLateData is a DataStream WindowOperator setting (SQL "
@@ -5009,7 +5128,7 @@ int fg_set_late_output(fg_handle* h, int32_t on) {
 
 int fg_collect_late(fg_handle* h, int32_t out_location, fg_late_records* out) {
     if (!h || !out) return FG_EINVAL;
-    h->snap.plan_valid = false;
+    h->snap.invalidate();
     if (out_location != FG_HOST && out_location != FG_DEVICE)
         return h->fail(FG_EINVAL, "fg_collect_late: unknown location %d", out_location);
     if (!h->late_out) return h->fail(FG_ESTATE, "fg_collect_late: the late output is off (fg_set_late_output)");
@@ -5063,7 +5182,7 @@ int fg_collect_late(fg_handle* h, int32_t out_location, fg_late_records* out) {
 
 int fg_snapshot_key_groups(fg_handle* h, fg_image_key_groups* out) {
     if (!h || !out) return FG_EINVAL;
-    h->snap.plan_valid = false;
+    h->snap.invalidate();
     if (!h->snap.img_ready) return h->fail(FG_ESTATE, "fg_snapshot_key_groups: no image returned since the last snapshot call");
     if (!h->snap.grouped) return h->fail(FG_ESTATE, "fg_snapshot_key_groups: the image was taken with grouping off");
     out->n_slices = (int64_t)h->snap.img.size();
@@ -5074,7 +5193,7 @@ int fg_snapshot_key_groups(fg_handle* h, fg_image_key_groups* out) {
 
 int fg_snapshot_slices(fg_handle* h, fg_image_slices* out) {
     if (!h || !out) return FG_EINVAL;
-    h->snap.plan_valid = false;
+    h->snap.invalidate();
     if (!h->snap.img_ready) return h->fail(FG_ESTATE, "fg_snapshot_slices: no image returned since the last snapshot call");
     h->snap.img.point(out);
     return FG_OK;
@@ -5095,7 +5214,7 @@ static int snapshot_full(fg_handle* h, const char* fn) {
     if (int rc = snapshot_enter(h, fn)) return rc;
     if (int rc = snapshot_plan(h)) return rc;
     const int rc = snapshot_export(h, fn, nullptr);
-    h->snap.plan_valid = false;   // (an export that failed its limits leaves its plan)
+    h->snap.invalidate();   // (an export that failed its limits leaves its plan)
     return rc;
 }
 
@@ -5111,20 +5230,20 @@ static int snapshot_select(fg_handle* h, const char* fn, const uint8_t* want, in
 }
 
 int fg_snapshot_state_async(fg_handle* h) {
-    if (h) h->snap.plan_valid = false;
+    if (h) h->snap.invalidate();
     return snapshot_full(h, "fg_snapshot_state_async");
 }
 
 int fg_snapshot_state_wait(fg_handle* h, fg_state_rows* out, int64_t* timer_watermark) {
     if (!h || !out) return FG_EINVAL;
-    h->snap.plan_valid = false;
+    h->snap.invalidate();
     HIPCHK(h, hipSetDevice(h->device));
     return snapshot_end(h, out, timer_watermark);
 }
 
 int fg_snapshot_state(fg_handle* h, fg_state_rows* out, int64_t* timer_watermark) {
     if (!h || !out) return FG_EINVAL;
-    h->snap.plan_valid = false;
+    h->snap.invalidate();
     if (int rc = snapshot_full(h, "fg_snapshot_state")) return rc;
     return snapshot_end(h, out, timer_watermark);
 }
@@ -5423,14 +5542,14 @@ static int restore_images(fg_handle* h, const char* fn, const fg_state_rows* ima
 
 int fg_restore(fg_handle* h, const fg_state_rows* in, int64_t timer_watermark) {
     if (!h || !in) return FG_EINVAL;
-    h->snap.plan_valid = false;
+    h->snap.invalidate();
     return restore_images(h, "fg_restore", in, 1, FG_HOST, false, 0, timer_watermark, nullptr);
 }
 
 int fg_restore_range(fg_handle* h, const fg_state_rows* images, int32_t n_images, int32_t location, int32_t key_hash,
                      int64_t timer_watermark, fg_restore_info* info) {
     if (!h) return FG_EINVAL;
-    h->snap.plan_valid = false;
+    h->snap.invalidate();
     if (n_images < 0 || (n_images > 0 && !images))
         return h->fail(FG_EINVAL, "fg_restore_range: %d images", n_images);
     if (location != FG_HOST && location != FG_DEVICE)
@@ -5473,7 +5592,7 @@ int fg_synchronize(fg_handle* h) {
 
 int fg_reset(fg_handle* h) {
     if (!h) return FG_EINVAL;
-    h->snap.plan_valid = false;
+    h->snap.invalidate();
     HIPCHK(h, hipSetDevice(h->device));
     if (int rc0 = settle_pending(h)) return rc0;
     int rc = sync(h);
@@ -5519,12 +5638,13 @@ int fg_kernel_stats(fg_handle* h, fg_kernel_stat* out, int32_t max, int32_t* cou
     int rc = sync(h, true);
     if (rc) return rc;
     // (late_out is listed for handles that had the late output on, topn -- after it -- for handles
-    // that had the selection on: the list of every other handle is what it was before the classes
-    // existed)
-    static_assert(K_LATE_OUT == K_NCLASS - 2 && K_TOPN == K_NCLASS - 1, "late_out and topn are the last classes");
+    // that had the selection on, pack_rows -- last -- for handles that packed rows: the list of every
+    // other handle is what it was before the classes existed)
+    static_assert(K_LATE_OUT == K_NCLASS - 3 && K_TOPN == K_NCLASS - 2 && K_PACK == K_NCLASS - 1,
+                  "late_out, topn and pack_rows are the last classes");
     int at = 0;
     for (int c = 0; c < K_NCLASS; c++) {
-        if ((c == K_LATE_OUT && !h->lo_listed) || (c == K_TOPN && !h->tp_listed)) continue;
+        if ((c == K_LATE_OUT && !h->lo_listed) || (c == K_TOPN && !h->tp_listed) || (c == K_PACK && !h->pk_listed)) continue;
         if (at < max) {
             std::memset(&out[at], 0, sizeof(fg_kernel_stat));
             std::snprintf(out[at].name, sizeof out[at].name, "%s", kClassName[c]);

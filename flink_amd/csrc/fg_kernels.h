@@ -715,4 +715,25 @@ struct Topn {
 };
 hipError_t launch_topn(const Topn& p, hipStream_t s);   // candidates, merge, final + gather
 
+// The fired rows as packed BinaryRowData rows (fg_fired_packed, fg_pack.hip): rows [first, first + n)
+// of the columns a call handed back, transposed into rows of arity + 1 words -- the bit set, then
+// [key,] agg[0 .. num_aggs), window_start, window_end. One launch.
+struct PackRows {
+    int64_t first, n;            // first + n <= the rows of the columns
+    int32_t num_aggs;
+    int32_t key_field;           // 1: the key is field 0 (FG_PACK_KEY_FIELD)
+    int32_t n_runs;              // > 0: run mode -- the windows come from the directory, ws / we are NULL
+    int32_t pad;
+    const int64_t* key;
+    const uint8_t* null_mask;
+    const int64_t* agg[kMaxAggs];
+    const int64_t* ws;
+    const int64_t* we;
+    const int64_t* run_first;    // [n_runs] ascending, run_first[0] = 0: the directory of all the call's rows
+    const int64_t* run_ws;
+    const int64_t* run_we;
+    unsigned long long* rows;    // [n * (arity + 1)] 8-byte words
+};
+hipError_t launch_pack_rows(const PackRows& p, hipStream_t s);
+
 }  // namespace fg

@@ -47,3 +47,24 @@ def pack_rows(fields, nulls=None, stride: int | None = None, row_kind: int = 0) 
         out[:, w // 8 + f] = v
     out[:, : w // 8] = bits.view(np.int64).reshape(n, w // 8)
     return out.view(np.uint8).reshape(-1)
+
+
+def unpack_rows(buf, arity: int, stride: int | None = None):
+    """The inverse of pack_rows: buf holds n rows of `arity` fixed-length fields, `stride` bytes apart
+    (default: the fixed-length part). Returns (fields, nulls, row_kind): `arity` int64 columns (the 8
+    bytes of each field; .view(np.float64) for a DOUBLE), a bool NULL column per field (bit 8 + f of
+    the bit set) and the RowKind byte of every row."""
+    w = bit_set_width(arity)
+    stride = stride or fixed_part_size(arity)
+    assert stride >= fixed_part_size(arity) and stride % 8 == 0
+    b = np.ascontiguousarray(np.frombuffer(buf, dtype=np.uint8) if isinstance(buf, (bytes, bytearray)) else buf,
+                             dtype=np.uint8).reshape(-1)
+    assert b.size % stride == 0, "a whole number of rows"
+    rows = b.reshape(-1, stride)
+    words = rows.view(np.int64)   # (n, stride / 8)
+    fields = [words[:, w // 8 + f].copy() for f in range(arity)]
+    nulls = []
+    for f in range(arity):
+        bit = HEADER_SIZE_IN_BITS + f
+        nulls.append((rows[:, bit >> 3] >> np.uint8(bit & 7)) & 1 == 1)
+    return fields, nulls, rows[:, 0].copy()

@@ -454,6 +454,55 @@ class WindowAggOperator:
             idx = int(agg)
         L.check(self._lib.fg_set_fired_topn(self._h, int(n), idx, 1 if descending else 0), self._h)
 
+    # -- fired rows as packed BinaryRowData rows ----------------------------------------------------
+    def fired_packed(self, first_row: int = 0, max_rows: int | None = None, key_field: bool = False,
+                     device: bool = False) -> dict:
+        """fg_fired_packed: rows [first_row, first_row + max_rows) of the rows the last
+        process_watermark / collect_fired returned (max_rows=None: all from first_row on), packed on
+        the GPU into BinaryRowData rows of the fields [key,] aggregates, window_start, window_end
+        (flink_amd.rows.unpack_rows reads them). Returns {"rows", "key", "n", "arity", "stride"}:
+        `rows` a uint8 numpy array of n * stride bytes and `key` the rows' int64 key column (None with
+        key_field, where the key is field 0) -- or with device=True the two device pointers (ints;
+        packed_to_host copies them), valid until the next fired_packed or the next call that fires,
+        takes a batch or otherwise invalidates the fired rows. Refused (WindowSpecError) for a
+        DataStream or local_partials operator and a range outside the rows, and (FlinkGpuError,
+        FG_ESTATE) unless the fired rows are still the ones the last returning call handed back."""
+        r = L.FgPackedRows()
+        mx = (1 << 62) if max_rows is None else int(max_rows)
+        L.check(self._lib.fg_fired_packed(self._h, int(first_row), mx, L.PACK_KEY_FIELD if key_field else 0,
+                                          L.DEVICE if device else L.HOST, C.byref(r)), self._h)
+        n, stride = int(r.n), int(r.stride)
+        out = {"n": n, "arity": int(r.arity), "stride": stride}
+        if device:
+            out["rows"], out["key"] = int(r.rows or 0), (None if key_field else int(r.key or 0))
+            return out
+        if n == 0:
+            out["rows"], out["key"] = np.zeros(0, dtype=np.uint8), (None if key_field else np.zeros(0, dtype=np.int64))
+            return out
+        out["rows"] = np.ctypeslib.as_array(C.cast(r.rows, C.POINTER(C.c_uint8)), shape=(n * stride,)).copy()
+        out["key"] = None if key_field else \
+            np.ctypeslib.as_array(C.cast(r.key, C.POINTER(C.c_int64)), shape=(n,)).copy()
+        return out
+
+    def packed_to_host(self, p: dict) -> dict:
+        """Host copy of a fired_packed(device=True) answer, in the form of the host answer."""
+        import torch
+
+        class _Col:
+            def __init__(self, ptr, typestr, n):
+                self.__cuda_array_interface__ = {"shape": (n,), "typestr": typestr, "data": (int(ptr), False),
+                                                 "version": 2}
+
+        n, dev = p["n"], torch.device("cuda", self.cfg.device_id)
+        torch.cuda.synchronize(self.cfg.device_id)   # (the rows are complete in stream order on the engine's stream)
+        out = dict(p)
+        if n == 0:
+            out["rows"], out["key"] = np.zeros(0, dtype=np.uint8), (None if p["key"] is None else np.zeros(0, dtype=np.int64))
+            return out
+        out["rows"] = torch.as_tensor(_Col(p["rows"], "|u1", n * p["stride"]), device=dev).cpu().numpy()
+        out["key"] = None if p["key"] is None else torch.as_tensor(_Col(p["key"], "<i8", n), device=dev).cpu().numpy()
+        return out
+
     # -- late elements as a side output -----------------------------------------------------------
     def set_late_output(self, on: bool = True):
         """fg_set_late_output (WindowedStream.sideOutputLateData): while on, every element the

@@ -540,6 +540,63 @@ int  fg_collect_late(fg_handle* h, int32_t out_location, fg_late_records* out);
  *    set of the output columns sized by n x (windows per call), not by the fired rows. */
 #define FG_TOPN_MAX 1024
 int  fg_set_fired_topn(fg_handle* h, int32_t n, int32_t agg_index, int32_t descending);
+/* Fired rows as packed BinaryRowData rows (ABI 16, added): the output half of fg_add_rows. The rows
+ * the last returning call -- fg_advance_progress, fg_collect_fired or fg_collect_fired_to -- handed
+ * back, transposed on the device into the fixed-length parts of BinaryRowData rows, which a shim
+ * views with BinaryRowData.pointTo instead of building one GenericRowData per row on the host. The
+ * intended use: take the fired rows with FG_DEVICE (nothing is copied), then pull them packed.
+ * fg_fired_packed(h, first_row, max_rows, flags, out_location, out) packs rows
+ * [first_row, min(first_row + max_rows, N)), N = that call's fg_rows.n. The range is there because a
+ * JVM direct buffer holds less than 2 GiB: a shim pulls a large fire in chunks, each call on its own.
+ *  - Row layout, byte-exact, the layout of fg_row_batch: little endian; a bit set of
+ *    ((arity + 71) / 64) * 8 bytes (8 for every arity here) whose byte 0 is RowKind INSERT = 0 and
+ *    whose bit 8 + f marks field f NULL; then 8 bytes per field. Fields:
+ *    [key,] agg[0] .. agg[num_aggs - 1], window_start, window_end -- arity = num_aggs + 2, one more
+ *    with FG_PACK_KEY_FIELD; stride = calculateFixPartSizeInBytes(arity) = 8 * (arity + 1). An
+ *    aggregate is the 8 bytes of fg_rows.agg[] (BIGINT, or the bits of a DOUBLE), the window fields
+ *    are TIMESTAMP(3) compact epoch milliseconds, the values fg_rows.window_start / window_end hold
+ *    (or would hold). A NULL aggregate (its null_mask bit) sets its field's bit and stores eight
+ *    zero bytes (BinaryRowWriter.setNullAt): whatever the column holds there does not reach the row.
+ *  - key: the rows' key column (for the ids of a key dictionary: the ids; the key rows come from
+ *    fg_key_dict_rows), at the location of `rows`; NULL with FG_PACK_KEY_FIELD, where the key (or
+ *    id) is field 0, a BIGINT.
+ *  - Run mode (fg_set_fired_runs): the window columns do not exist; the window of a row is its
+ *    run's, looked up on the device in the run directory fg_fired_runs describes (uploaded once per
+ *    call; one launch covers every run).
+ *  - Top-N (fg_set_fired_topn): the packed rows are the selected rows, in their order.
+ *  - FG_HOST: rows (and key) are library-owned pinned host memory, complete when the call returns.
+ *    FG_DEVICE: device memory, complete in stream order on fg_stream. Both stay valid until the
+ *    next fg_fired_packed or the next call that invalidates the fired rows (below). The buffers are
+ *    reused and grow to the largest range asked for.
+ *  - FG_EINVAL, before any device work (fg_last_error names the reason; the handle stays usable):
+ *    NULL h or out, an unknown location; flag bits other than FG_PACK_KEY_FIELD; first_row < 0,
+ *    first_row > N or max_rows < 0; n * stride >= 2^31 with FG_HOST (ask for a smaller range); an
+ *    FG_MODE_DATASTREAM handle, whose elements are tuples, not RowData; an FG_FLAG_LOCAL_PARTIALS
+ *    handle, whose rows are accumulator rows of another layout.
+ *  - FG_ESTATE unless the fired rows are still the ones the last returning call handed back: no
+ *    returning call yet; any call on the handle since then other than fg_fired_runs,
+ *    fg_fired_packed, fg_get_stats, fg_late_dropped, fg_kernel_stats, fg_set_kernel_timing,
+ *    fg_synchronize, fg_stream, fg_last_error and fg_snapshot_plan (the calls a valid
+ *    fg_snapshot_plan survives, and fg_fired_runs); a pending fg_advance_progress_async fire or
+ *    uncollected async rows. A returning call that fired nothing is valid and gives n = 0, as do
+ *    first_row == N and max_rows == 0.
+ *  - One kernel launch per call with rows, on the handle's stream, one lane per 8-byte word of the
+ *    output; per row it reads 8 * arity + 1 bytes (8 * (arity - 2) + 1 in run mode) and writes
+ *    8 * (arity + 1). fg_kernel_stats class "pack_rows": records = rows = rows packed; listed for a
+ *    handle once it has packed rows, after every other class, "late_out" and "topn" included (a
+ *    handle that never packs lists what it listed before the class existed). */
+enum fg_pack_flags { FG_PACK_KEY_FIELD = 1 };
+typedef struct fg_packed_rows {
+    int64_t n;             /* rows packed */
+    int32_t location;      /* fg_location of rows / key */
+    int32_t arity;         /* fields per row */
+    int32_t stride;        /* bytes per row = calculateFixPartSizeInBytes(arity) */
+    int32_t flags;         /* as passed */
+    const uint8_t* rows;   /* n * stride bytes */
+    const int64_t* key;    /* the rows' key column (dictionary handles: the ids); NULL with FG_PACK_KEY_FIELD */
+} fg_packed_rows;
+int  fg_fired_packed(fg_handle* h, int64_t first_row, int64_t max_rows, int32_t flags,
+                     int32_t out_location, fg_packed_rows* out);
 /* Selective images (ABI 16, added): a checkpoint that exports and copies only the slices its caller
  * needs. The engine says what is resident and what changed (plan), the caller answers with a mask
  * (a shim's policy needs more than the changed slices: a CUMULATE namespace is rebuilt from all its

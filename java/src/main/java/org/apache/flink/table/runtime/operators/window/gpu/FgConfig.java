@@ -72,6 +72,14 @@ public final class FgConfig {
     public static final String FIRED_TOPN_KEY = "table.exec.window-agg.gpu.fired-topn";
     public static String firedTopN = System.getProperty(FIRED_TOPN_KEY);
 
+    /**
+     * Packed fired rows (fg_fired_packed): the fired rows stay on the device and are pulled as packed
+     * BinaryRowData rows, emitted as BinaryRowData.pointTo views instead of one GenericRowData per row.
+     * SQL handles without a local phase only. Off by default.
+     */
+    public static final String FIRED_PACKED_KEY = "table.exec.window-agg.gpu.fired-packed";
+    public static boolean firedPacked = Boolean.parseBoolean(System.getProperty(FIRED_PACKED_KEY, "false"));
+
     /** {n, aggIndex, descending ? 1 : 0} of a fired-topn value; null when unset or n = 0 */
     public static int[] parseFiredTopN(String v) {
         if (v == null || v.trim().isEmpty()) {

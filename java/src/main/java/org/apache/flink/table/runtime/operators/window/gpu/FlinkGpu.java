@@ -113,6 +113,26 @@ public final class FlinkGpu {
      */
     public static native void setFiredTopN(long h, int n, int aggIndex, boolean descending);
 
+    /** fg_advance_progress(FG_DEVICE): the fired rows stay on the device (nothing is copied); their count. */
+    public static native long advanceProgressDevice(long h, long watermark);
+
+    /** fg_collect_fired: as {@link #collectFired}, the rows left on the device; their count. */
+    public static native long collectFiredDevice(long h);
+
+    /** fg_pack_flags: the key (or dictionary id) is field 0 of the packed rows */
+    public static final int PACK_KEY_FIELD = 1;
+
+    /**
+     * fg_fired_packed(FG_HOST) (ABI 16): rows [firstRow, firstRow + maxRows) of the rows the last
+     * advanceProgress* / collectFired* returned, packed on the GPU into the fixed-length parts of
+     * BinaryRowData rows of the fields [key,] agg[0..), window_start, window_end (BinaryRowData.pointTo
+     * views them). out[0]: the rows (n * stride bytes), out[1]: their key column (null with
+     * PACK_KEY_FIELD) -- library-owned host memory, valid until the next firedPacked or the next call
+     * that changes the fired rows. shape: {arity, stride}. Returns n. IllegalArgumentException for a
+     * range outside the rows and for DataStream / FG_FLAG_LOCAL_PARTIALS handles.
+     */
+    public static native long firedPacked(long h, long firstRow, long maxRows, int flags, ByteBuffer[] out, long[] shape);
+
     /**
      * fg_set_late_output (ABI 16): WindowedStream.sideOutputLateData -- every element the handle
      * would count in {@link #lateDropped} is kept instead and returned by {@link #collectLate}; the

@@ -37,6 +37,8 @@ import org.apache.flink.api.common.state.ValueStateDescriptor;
 import org.apache.flink.api.common.typeutils.TypeSerializer;
 import org.apache.flink.api.common.typeutils.base.LongSerializer;
 import org.apache.flink.api.java.tuple.Tuple2;
+import org.apache.flink.core.memory.MemorySegment;
+import org.apache.flink.core.memory.MemorySegmentFactory;
 import org.apache.flink.metrics.Counter;
 import org.apache.flink.runtime.state.CheckpointableKeyedStateBackend;
 import org.apache.flink.runtime.state.KeyGroupRange;
@@ -95,6 +97,8 @@ public final class GpuSlicingWindowProcessor implements SlicingWindowProcessor<L
     private transient boolean batchHanded;
     /** the handle is in run mode (FgConfig.firedRuns): fired rows carry no window columns */
     private transient boolean firedRuns;
+    /** the fired rows are pulled as packed BinaryRowData rows (FgConfig.firedPacked, fg_fired_packed) */
+    private transient boolean firedPacked;
     /** the namespaces the backend holds from the last image written (or restored), and their slices */
     private transient Map<Long, Set<Long>> imageContrib;
     /** the next window end the key timers of fired state were registered at */
@@ -131,6 +135,7 @@ public final class GpuSlicingWindowProcessor implements SlicingWindowProcessor<L
         if (firedRuns) {
             FlinkGpu.setFiredRuns(handle, true);
         }
+        firedPacked = FgConfig.firedPacked && (spec.flags & FgConfig.FLAG_LOCAL_PARTIALS) == 0;
         keys = new GpuKeyRows(spec, maxP);
         accRows = new GpuAccRows(spec.aggs, spec.valType);
         int b = spec.batchRecords;
@@ -280,6 +285,10 @@ public final class GpuSlicingWindowProcessor implements SlicingWindowProcessor<L
     public void advanceProgress(long progress) throws Exception {
         flushBatch();
         collectHeld();   // (an operator's async progress: its rows first, in order)
+        if (firedPacked) {
+            emitPacked(FlinkGpu.advanceProgressDevice(handle, progress));
+            return;
+        }
         ByteBuffer[] cols = new ByteBuffer[5 + spec.aggs.length];
         emit(cols, FlinkGpu.advanceProgress(handle, progress, cols));
     }
@@ -297,6 +306,10 @@ public final class GpuSlicingWindowProcessor implements SlicingWindowProcessor<L
             return;
         }
         asyncPending = false;
+        if (firedPacked) {
+            emitPacked(FlinkGpu.collectFiredDevice(handle));
+            return;
+        }
         ByteBuffer[] cols = new ByteBuffer[5 + spec.aggs.length];
         emit(cols, FlinkGpu.collectFired(handle, cols));
     }
@@ -342,6 +355,51 @@ public final class GpuSlicingWindowProcessor implements SlicingWindowProcessor<L
             aggs.setField(nAggs + 1, runs != null ? runEnd : TimestampData.fromEpochMillis(cols[2].getLong(8 * i)));
             ctx.output(new JoinedRowData(keyRows[i], aggs));
         }
+        countLateDrops();
+    }
+
+    /** packed chunks hold at most this many bytes (a direct buffer holds less than 2 GiB) */
+    private static final long PACKED_CHUNK_BYTES = 1L << 30;
+
+    /**
+     * The n fired rows, left on the device by advanceProgressDevice / collectFiredDevice, pulled as
+     * packed BinaryRowData rows (fg_fired_packed) in chunks of at most 1 GiB and emitted as pointTo
+     * views of one byte[] per chunk (the rows outlive the library's reused buffer). BIGINT key: one
+     * flat row [key, aggs..., window_start, window_end] in place of the JoinedRowData; dictionary key:
+     * JoinedRowData(key row of the id, [aggs..., window_start, window_end]).
+     */
+    private void emitPacked(long n) {
+        final boolean flat = spec.bigintKey;
+        final int arity = spec.aggs.length + 2 + (flat ? 1 : 0);
+        final int stride = 8 * (arity + 1);   // calculateFixPartSizeInBytes: an 8-byte bit set up to 56 fields
+        final long chunkRows = PACKED_CHUNK_BYTES / stride;
+        final ByteBuffer[] out = new ByteBuffer[2];
+        final long[] shape = new long[2];
+        for (long first = 0; first < n; ) {
+            final int m =
+                    (int) FlinkGpu.firedPacked(handle, first, chunkRows, flat ? FlinkGpu.PACK_KEY_FIELD : 0, out, shape);
+            if (m <= 0 || shape[0] != arity || shape[1] != stride) {
+                throw new IllegalStateException(
+                        "firedPacked: " + m + " rows of arity " + shape[0] + ", stride " + shape[1] + " at row " + first
+                                + " of " + n);
+            }
+            final byte[] all = new byte[m * stride];   // (the rows outlive the reused buffer)
+            out[0].position(0);
+            out[0].get(all);
+            final MemorySegment seg = MemorySegmentFactory.wrap(all);
+            final RowData[] keyRows = flat ? null : keys.rows(out[1].order(ByteOrder.nativeOrder()), m);
+            for (int i = 0; i < m; i++) {
+                final BinaryRowData row = new BinaryRowData(arity);
+                row.pointTo(seg, i * stride, stride);
+                ctx.output(flat ? row : new JoinedRowData(keyRows[i], row));
+            }
+            first += m;
+        }
+        countLateDrops();
+    }
+
+    /** the engine's new late drops into the operator's numLateRecordsDropped */
+    private void countLateDrops() {
         long dropped = FlinkGpu.lateDropped(handle);
         if (lateDropped != null && dropped > droppedSeen) {
             lateDropped.inc(dropped - droppedSeen);

@@ -13,6 +13,9 @@
  *   advanceProgressAsync fg_advance_progress_async (the same, the fires queued: the watermark held)
  *   advanceProgressAsyncN fg_advance_progress_async_n (a batch's held watermarks in one call)
  *   collectFired    fg_collect_fired_to  (the held watermark's rows, in host memory; then the watermark is forwarded)
+ *   advanceProgressDevice / collectFiredDevice   fg_advance_progress / fg_collect_fired with FG_DEVICE (the rows
+ *                   stay on the device: nothing is copied) and
+ *   firedPacked     fg_fired_packed      (... pulled as packed BinaryRowData rows, a range at a time)
  *   flush           fg_flush             (prepareSnapshotPreBarrier)
  *   flushPartials   fg_flush_partials    (local phase: WindowBuffer.flush of LocalSlicingWindowAggOperator)
  *   snapshotState   fg_snapshot_state    (snapshotState: the window-aggs image)
@@ -258,6 +261,50 @@ JNIEXPORT jlong JNICALL FN(collectFired)(JNIEnv* env, jclass cls, jlong hp, jobj
     fg_rows r;
     if (check(env, h, fg_collect_fired_to(h, FG_HOST, &r))) return 0;
     return put_rows(env, &r, cols, "collectFired");
+}
+
+/* long advanceProgressDevice(long h, long watermark): fg_advance_progress with FG_DEVICE -- the fired
+ * rows stay on the device (no column is copied); returns their count. firedPacked pulls them. */
+JNIEXPORT jlong JNICALL FN(advanceProgressDevice)(JNIEnv* env, jclass cls, jlong hp, jlong wm) {
+    (void)cls;
+    fg_handle* h = (fg_handle*)(intptr_t)hp;
+    fg_rows r;
+    if (check(env, h, fg_advance_progress(h, wm, FG_DEVICE, &r))) return 0;
+    return r.n;
+}
+
+/* long collectFiredDevice(long h): fg_collect_fired -- as collectFired, the rows left on the device */
+JNIEXPORT jlong JNICALL FN(collectFiredDevice)(JNIEnv* env, jclass cls, jlong hp) {
+    (void)cls;
+    fg_handle* h = (fg_handle*)(intptr_t)hp;
+    fg_rows r;
+    if (check(env, h, fg_collect_fired(h, &r))) return 0;
+    return r.n;
+}
+
+/* long firedPacked(long h, long firstRow, long maxRows, int flags, ByteBuffer[] out, long[] shape):
+ * rows [firstRow, firstRow + maxRows) of the rows the last advanceProgress* / collectFired* returned as
+ * packed BinaryRowData rows (fg_fired_packed FG_HOST, ABI 16). out[0]: the rows, n * stride bytes;
+ * out[1]: their key column (null with FG_PACK_KEY_FIELD = 1 in flags: the key is field 0) -- library-owned
+ * host memory, valid until the next firedPacked or the next call that changes the fired rows. shape
+ * (length >= 2, may be null): {arity, stride}. Returns n. */
+JNIEXPORT jlong JNICALL FN(firedPacked)(JNIEnv* env, jclass cls, jlong hp, jlong firstRow, jlong maxRows, jint flags,
+                                        jobjectArray out, jlongArray shape) {
+    (void)cls;
+    fg_handle* h = (fg_handle*)(intptr_t)hp;
+    if (!out || (*env)->GetArrayLength(env, out) < 2 || (shape && (*env)->GetArrayLength(env, shape) < 2)) {
+        throw_code(env, FG_EINVAL, "firedPacked: out needs 2 entries, shape 2");
+        return 0;
+    }
+    fg_packed_rows r;
+    if (check(env, h, fg_fired_packed(h, firstRow, maxRows, (int32_t)flags, FG_HOST, &r))) return 0;
+    (*env)->SetObjectArrayElement(env, out, 0, wrap(env, r.rows, r.n * r.stride));
+    (*env)->SetObjectArrayElement(env, out, 1, r.key ? wrap(env, r.key, 8 * r.n) : NULL);
+    if (shape) {
+        const jlong sh[2] = {r.arity, r.stride};
+        (*env)->SetLongArrayRegion(env, shape, 0, 2, sh);
+    }
+    return r.n;
 }
 
 /* void setFiredRuns(long h, boolean on): run mode (fg_set_fired_runs, ABI 16) -- the fired rows come
