@@ -129,6 +129,16 @@ class FgKeyDictStats(C.Structure):
         "live", "issued", "free_ordinals", "arena_bytes", "table_slots", "side_rows", "retired_total", "reserved0")]
 
 
+FIELD_FIX1, FIELD_FIX2, FIELD_FIX4, FIELD_FIX8, FIELD_VAR = 1, 2, 4, 8, 16   # fg_field_kind
+PROJ_MAX_KEY_FIELDS, PROJ_MAX_COLS = 8, 4
+
+
+class FgRowProjection(C.Structure):
+    _fields_ = [("arity", C.c_int32), ("n_key_fields", C.c_int32), ("key_field", C.c_int32 * PROJ_MAX_KEY_FIELDS),
+                ("key_kind", C.c_int32 * PROJ_MAX_KEY_FIELDS), ("n_cols", C.c_int32),
+                ("col_field", C.c_int32 * PROJ_MAX_COLS)]
+
+
 class FgKernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("launches", C.c_int64), ("total_ms", C.c_double),
                 ("records", C.c_int64), ("rows", C.c_int64)]
@@ -162,7 +172,7 @@ EXPORTS = (
     "fg_comm_set_key_dicts", "fg_key_dict_arena",
     "fg_key_dict_copy_arena", "fg_key_dict_size", "fg_key_dict_stream", "fg_key_dict_set_timing",
     "fg_key_dict_kernel_stats", "fg_key_dict_last_error", "fg_key_dict_close",
-    "fg_key_dict_get_stats", "fg_key_dict_retain",
+    "fg_key_dict_get_stats", "fg_key_dict_retain", "fg_key_dict_project", "fg_key_dict_intern_fields",
     "fg_binaryrow_hash", "fg_host_register", "fg_host_unregister",
     "fg_comm_unique_id", "fg_comm_open", "fg_comm_exchange_columns", "fg_comm_exchange_partials",
     "fg_comm_exchange_fired", "fg_comm_exchange_flushed", "fg_comm_round_begin", "fg_comm_round_exchange",
@@ -305,6 +315,12 @@ def load():
         L.fg_key_dict_retain.argtypes = [P, C.c_int32, C.c_int32, C.POINTER(P), C.POINTER(C.c_int64),
                                          C.POINTER(FgKeyDictStats)]
         L.fg_key_dict_get_stats.restype = L.fg_key_dict_retain.restype = C.c_int
+    if hasattr(L, "fg_key_dict_project"):   # (the same)
+        L.fg_key_dict_project.argtypes = [P, C.c_int32, C.c_int64, P, C.c_int64, P, P, C.POINTER(FgRowProjection), P,
+                                          C.c_int64, P, P, C.POINTER(P), C.POINTER(P), C.POINTER(C.c_int64)]
+        L.fg_key_dict_intern_fields.argtypes = [P, C.c_int32, C.c_int64, P, C.c_int64, P, P, C.POINTER(FgRowProjection),
+                                                P, P, C.POINTER(P), C.POINTER(P)]
+        L.fg_key_dict_project.restype = L.fg_key_dict_intern_fields.restype = C.c_int
     L.fg_selftest.argtypes = [C.c_int32, C.c_char_p, C.c_int32]
     L.fg_selftest.restype = C.c_int
     L.fg_comm_bytes_sent.argtypes = [P]

@@ -32,6 +32,9 @@
 // owner and gathers their key rows in the grouped order (the same k_rows_* pipeline on the caller's
 // stream, k_owner_byte_counts for the bytes per owner), and keydict_intern_packed (fg_keydict.h)
 // checks and scans the lengths an owner received (k_recv_lengths) and interns the rows.
+// The key rows themselves can be made on the GPU: fg_key_dict_project / fg_key_dict_intern_fields
+// project them from packed BinaryRowData records (the key selector; kernels in fg_keyproj.hip, the
+// offsets by the same scan, fg_rows_scan.h) and intern them from the dictionary's scratch.
 // An entry lasts until fg_key_dict_retain retires it: the caller lists the ids that still hold
 // state, every other entry leaves the table and the arena (k_retain_*), and k_dict_assign hands
 // the retired ordinals out again before it issues a fresh one -- the dictionary is bounded by the
@@ -51,6 +54,8 @@
 #include "../../include/flinkgpu.h"
 #include "fg_kernels.h"
 #include "fg_keydict.h"
+#include "fg_keyproj.h"
+#include "fg_rows_scan.h"
 #include "fg_window.h"
 
 using namespace fg;
@@ -510,37 +515,10 @@ __global__ __launch_bounds__(kDictThreads) void k_dict_gather(DictDev d, int64_t
 // out_lengths, each block's padded bytes), k_rows_scan_sums (one workgroup: the exclusive scan of
 // the block sums, the total) and k_rows_offsets (out_offsets[0..n)); 64-bit throughout. The host
 // reads RowsCtr once, checks the capacity and the bad ids, and only then launches k_rows_copy.
+// (RowsCtr, padded8, the block scan, k_rows_scan_sums and k_rows_offsets: fg_rows_scan.h, shared with
+// fg_keyproj.hip; RowsCtr's bad rows are here the ids that are negative or past the dictionary's size)
 constexpr int kRowsBlock = kDictThreads;   // ids per scan block = rows per copy workgroup
-
-struct RowsCtr {
-    unsigned long long total;      // padded bytes of every row = out_offsets[n]
-    unsigned long long bad;        // ids that are negative or past the dictionary's size
-    unsigned long long bad_first;  // lowest index of such an id (~0: none)
-};
-
-__host__ __device__ __forceinline__ uint64_t padded8(int32_t len) { return ((uint64_t)(uint32_t)len + 7) & ~7ull; }
-
-// exclusive scan of v over the workgroup (s_wave: kDictThreads / 64 words, reusable on return)
-__device__ __forceinline__ uint64_t block_exclusive_scan_u64(uint64_t v, uint64_t* s_wave, uint64_t* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint64_t x = v;   // inclusive scan over the wave
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint64_t y = __shfl_up(x, off);
-        if (lane >= off) x += y;
-    }
-    if (lane == 63) s_wave[wave] = x;
-    __syncthreads();
-    uint64_t base = 0, t = 0;
-#pragma unroll
-    for (int k = 0; k < kDictThreads / 64; k++) {
-        const uint64_t w = s_wave[k];
-        if (k < wave) base += w;
-        t += w;
-    }
-    __syncthreads();
-    *total = t;
-    return base + x - v;
-}
+static_assert(kRowsBlock == kScanThreads, "fg_rows_scan.h scans blocks of kScanThreads rows");
 
 __global__ __launch_bounds__(kDictThreads) void k_rows_lengths(DictDev d, int64_t nids, int64_t n, const int64_t* ids,
                                                                int32_t* len_out, uint64_t* sums, RowsCtr* rc) {
@@ -561,34 +539,6 @@ __global__ __launch_bounds__(kDictThreads) void k_rows_lengths(DictDev d, int64_
     uint64_t total;
     (void)block_exclusive_scan_u64(padded8(len), s_wave, &total);
     if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-
-// one workgroup: sums[0..nb) -> their exclusive scan, the total to rc->total and off_out[n]
-__global__ __launch_bounds__(kDictThreads) void k_rows_scan_sums(uint64_t* sums, int64_t nb, RowsCtr* rc, int64_t* off_out,
-                                                                 int64_t n) {
-    __shared__ uint64_t s_wave[kDictThreads / 64];
-    uint64_t carry = 0;   // (the same in every thread)
-    for (int64_t b0 = 0; b0 < nb; b0 += kDictThreads) {
-        const int64_t b = b0 + threadIdx.x;
-        uint64_t total;
-        const uint64_t ex = block_exclusive_scan_u64(b < nb ? sums[b] : 0ull, s_wave, &total);
-        if (b < nb) sums[b] = carry + ex;
-        carry += total;
-    }
-    if (threadIdx.x == 0) {
-        rc->total = carry;
-        off_out[n] = (int64_t)carry;
-    }
-}
-
-__global__ __launch_bounds__(kDictThreads) void k_rows_offsets(int64_t n, const int32_t* len_in, const uint64_t* sums,
-                                                               int64_t* off_out) {
-    __shared__ uint64_t s_wave[kDictThreads / 64];
-    const int64_t i = (int64_t)blockIdx.x * kRowsBlock + threadIdx.x;
-    const int32_t len = i < n ? len_in[i] : 0;
-    uint64_t total;
-    const uint64_t ex = block_exclusive_scan_u64(len > 0 ? padded8(len) : 0ull, s_wave, &total);
-    if (i < n) off_out[i] = (int64_t)(sums[blockIdx.x] + ex);
 }
 
 // The copy, balanced by bytes: a workgroup owns kRowsBlock consecutive rows, whose output span
@@ -880,6 +830,11 @@ struct fg_key_dict {
     // ids, lengths, offsets and packed bytes; grown on demand and reused across calls
     Buf rows_ctr, rows_sums, rows_ids, rows_len, rows_off, rows_bytes;
     Buf part_scratch;                // fg_partition_keyed_by_owner: the owner partition's histogram and offsets
+    // fg_key_dict_project / _intern_fields: for FG_HOST callers the device records, columns and null
+    // bytes; the key rows' offsets, lengths and bytes (intern_fields, and FG_HOST project) and the
+    // ids and key groups of FG_HOST intern_fields; grown to the largest call
+    Buf pj_bytes, pj_off, pj_len, pj_cols, pj_null, pj_koff, pj_klen, pj_kbytes, pj_ids, pj_kg;
+    bool projected = false;          // a projection's length pass has run: kernel_stats lists "dict_project"
     hipEvent_t ev_order = nullptr;   // ... and the event that orders a caller's stream after the dictionary's
     std::unordered_map<std::string, int64_t> side;   // rows whose tag another row holds
     std::string err;
@@ -888,9 +843,10 @@ struct fg_key_dict {
     // dictionary's stream; summed into the three classes below
     bool timing = false;
     // ([7..10]: the two kernel stages of fg_key_dict_retain, "dict_retain"; [11..12]: a table rebuild --
-    // k_slots_clear + k_dict_rehash, when the table grows and inside a retain -- "dict_rebuild")
-    hipEvent_t ev[13] = {};
-    fg_kernel_stat kstat[5] = {};
+    // k_slots_clear + k_dict_rehash, when the table grows and inside a retain -- "dict_rebuild";
+    // [13..16]: the two kernel stages of a projection, "dict_project")
+    hipEvent_t ev[17] = {};
+    fg_kernel_stat kstat[6] = {};
     // fg_key_dict_intern_async: the lookup launched, the rest of the call taken by _wait
     struct Pending {
         bool active = false, host = false;
@@ -1419,6 +1375,203 @@ int fg_key_dict_rows(fg_key_dict* d, int32_t location, int64_t n, const int64_t*
     return FG_OK;
 }
 
+// fg_key_dict_project (intern false) and fg_key_dict_intern_fields (intern true): the arguments
+// checked, FG_HOST inputs staged, the length pass (fg_keyproj.hip), the one host read, then the key
+// rows written -- into the caller's buffer, or into the dictionary's scratch and interned from there.
+static int project_impl(fg_key_dict* d, bool intern, int32_t location, int64_t n, const uint8_t* bytes, int64_t nbytes,
+                        const int64_t* offsets, const int32_t* lengths, const fg_row_projection* proj, uint8_t* out_key_bytes,
+                        int64_t cap_bytes, int64_t* out_key_offsets, int32_t* out_key_lengths, int64_t* const* out_cols,
+                        uint8_t* const* out_col_null, int64_t* out_nbytes, int64_t* out_id, int32_t* out_kg) {
+    if (!d) return FG_EINVAL;
+    const std::string who = intern ? "fg_key_dict_intern_fields" : "fg_key_dict_project";
+    if (!proj) return d->fail(FG_EINVAL, who + ": a NULL projection");
+    if (location != FG_HOST && location != FG_DEVICE) return d->fail(FG_EINVAL, who + ": unknown location");
+    const bool host = location == FG_HOST;
+    if (n < 0 || n > 0x7fffffff || nbytes < 0 ||
+        (n > 0 && (!bytes || !offsets || !lengths ||
+                   (intern ? !out_id : (!out_key_offsets || !out_key_lengths || !out_nbytes)))))
+        return d->fail(FG_EINVAL, who + ": invalid arguments");
+    if (proj->arity < 1 || proj->arity > 32767 || proj->n_key_fields < 1 || proj->n_key_fields > FG_PROJ_MAX_KEY_FIELDS ||
+        proj->n_cols < 0 || proj->n_cols > FG_PROJ_MAX_COLS)
+        return d->fail(FG_EINVAL, who + ": arity in [1, 32767], 1..8 key fields and 0..4 columns expected");
+    ProjArgs a{};
+    a.n = n;
+    a.nbytes = nbytes;
+    a.in_bits = ((proj->arity + 63 + 8) / 64) * 8;
+    a.in_fixed = a.in_bits + 8 * proj->arity;
+    a.k = proj->n_key_fields;
+    a.n_cols = proj->n_cols;
+    for (int f = 0; f < a.k; f++) {
+        const int32_t kind = proj->key_kind[f];
+        if (proj->key_field[f] < 0 || proj->key_field[f] >= proj->arity)
+            return d->fail(FG_EINVAL, who + ": key field " + std::to_string(f) + " names no field of the input row");
+        if (kind != FG_FIELD_FIX1 && kind != FG_FIELD_FIX2 && kind != FG_FIELD_FIX4 && kind != FG_FIELD_FIX8 &&
+            kind != FG_FIELD_VAR)
+            return d->fail(FG_EINVAL, who + ": key field " + std::to_string(f) + " has an unknown kind");
+        a.key_field[f] = proj->key_field[f];
+        a.key_kind[f] = kind;
+    }
+    if (n > 0 && a.n_cols > 0 && !out_cols) return d->fail(FG_EINVAL, who + ": a NULL out_cols");
+    for (int c = 0; c < a.n_cols; c++) {
+        if (proj->col_field[c] < 0 || proj->col_field[c] >= proj->arity)
+            return d->fail(FG_EINVAL, who + ": column " + std::to_string(c) + " names no field of the input row");
+        if (n > 0 && !out_cols[c]) return d->fail(FG_EINVAL, who + ": a NULL column in out_cols");   // (columns of no row may be NULL)
+        a.col_field[c] = proj->col_field[c];
+    }
+    if (!intern && (cap_bytes < 0 || (cap_bytes > 0 && !out_key_bytes)))
+        return d->fail(FG_EINVAL, who + ": invalid arguments");
+    if (!host && ((uintptr_t)bytes % 8 != 0 || (!intern && (uintptr_t)out_key_bytes % 8 != 0)))
+        return d->fail(FG_EINVAL, who + ": device records and a device out_key_bytes must be 8-byte aligned");
+    if (d->pend.active) return d->fail(FG_ESTATE, who + ": an async intern is pending (fg_key_dict_intern_wait)");
+    if (n == 0) {
+        if (intern) return FG_OK;
+        if (out_nbytes) *out_nbytes = 0;
+        if (out_key_offsets && host) out_key_offsets[0] = 0;
+        if (out_key_offsets && !host) {   // (a device word: the only device work of an empty call)
+            if (hipSetDevice(d->device) != hipSuccess) return d->fail(FG_EDEVICE, "hipSetDevice failed");
+            DCHK(d, hipMemsetAsync(out_key_offsets, 0, 8, d->stream));
+            DCHK(d, hipStreamSynchronize(d->stream));
+        }
+        return FG_OK;
+    }
+    if (hipSetDevice(d->device) != hipSuccess) return d->fail(FG_EDEVICE, "hipSetDevice failed");
+    hipStream_t s = d->stream;
+    const int64_t nb = (n + kRowsBlock - 1) / kRowsBlock;
+    DCHK(d, d->rows_ctr.ensure(sizeof(RowsCtr), s));
+    DCHK(d, d->rows_sums.ensure(8 * (size_t)nb, s));
+    if (host) {
+        DCHK(d, d->pj_bytes.ensure((size_t)nbytes + 8, s));
+        DCHK(d, d->pj_off.ensure(8 * (size_t)n, s));
+        DCHK(d, d->pj_len.ensure(4 * (size_t)n, s));
+        if (nbytes) DCHK(d, hipMemcpyAsync(d->pj_bytes.p, bytes, (size_t)nbytes, hipMemcpyHostToDevice, s));
+        DCHK(d, hipMemcpyAsync(d->pj_off.p, offsets, 8 * (size_t)n, hipMemcpyHostToDevice, s));
+        DCHK(d, hipMemcpyAsync(d->pj_len.p, lengths, 4 * (size_t)n, hipMemcpyHostToDevice, s));
+        a.bytes = d->pj_bytes.as<uint8_t>();
+        a.off = d->pj_off.as<int64_t>();
+        a.len = d->pj_len.as<int32_t>();
+        if (a.n_cols) {
+            DCHK(d, d->pj_cols.ensure(8 * (size_t)n * a.n_cols, s));
+            DCHK(d, d->pj_null.ensure((size_t)n * a.n_cols, s));
+        }
+    } else {
+        a.bytes = bytes;
+        a.off = offsets;
+        a.len = lengths;
+    }
+    for (int c = 0; c < a.n_cols; c++) {
+        uint8_t* cn = out_col_null ? out_col_null[c] : nullptr;
+        a.out_col[c] = host ? d->pj_cols.as<int64_t>() + (size_t)c * n : out_cols[c];
+        a.out_null[c] = !cn ? nullptr : host ? d->pj_null.as<uint8_t>() + (size_t)c * n : cn;
+    }
+    int64_t* koff = out_key_offsets;
+    int32_t* klen = out_key_lengths;
+    if (host || intern) {
+        DCHK(d, d->pj_koff.ensure(8 * (size_t)(n + 1), s));
+        DCHK(d, d->pj_klen.ensure(4 * (size_t)n, s));
+        koff = d->pj_koff.as<int64_t>();
+        klen = d->pj_klen.as<int32_t>();
+    }
+    // 1) the length pass; then the one host read of the call: {total, bad rows, lowest bad index}
+    RowsCtr* rc = d->rows_ctr.as<RowsCtr>();
+    DCHK(d, hipMemsetAsync(rc, 0, offsetof(RowsCtr, bad_first), s));
+    DCHK(d, hipMemsetAsync(&rc->bad_first, 0xff, 8, s));
+    if (d->timing) DCHK(d, hipEventRecord(d->ev[13], s));
+    DCHK(d, keyproj_lengths_offsets(s, a, klen, koff, d->rows_sums.as<uint64_t>(), rc));
+    if (d->timing) DCHK(d, hipEventRecord(d->ev[14], s));
+    d->projected = true;
+    RowsCtr hc;
+    DCHK(d, hipMemcpyAsync(&hc, rc, sizeof hc, hipMemcpyDeviceToHost, s));
+    DCHK(d, hipStreamSynchronize(s));
+    float ms = 0.f;
+    if (d->timing) DCHK(d, hipEventElapsedTime(&ms, d->ev[13], d->ev[14]));
+    auto timed = [&](float t, int64_t written) {
+        if (!d->timing) return;
+        d->kstat[5].launches++;
+        d->kstat[5].total_ms += t;
+        d->kstat[5].records += n;
+        d->kstat[5].rows += written;
+    };
+    if (hc.bad) {
+        timed(ms, 0);
+        return d->fail(FG_EINVAL, who + ": " + std::to_string(hc.bad) +
+                                      " bad rows (an offset or length outside the buffer or not a multiple of 8, a row "
+                                      "shorter than its fixed-length part, a variable-length key field outside its row, a "
+                                      "key row above 2^24 - 4 bytes, or a NULL column without null bytes); the first at index " +
+                                      std::to_string(hc.bad_first));
+    }
+    const int64_t total = (int64_t)hc.total;
+    if (host) {   // straight into the caller's memory
+        for (int c = 0; c < a.n_cols; c++) {
+            DCHK(d, hipMemcpyAsync(out_cols[c], a.out_col[c], 8 * (size_t)n, hipMemcpyDeviceToHost, s));
+            if (a.out_null[c]) DCHK(d, hipMemcpyAsync(out_col_null[c], a.out_null[c], (size_t)n, hipMemcpyDeviceToHost, s));
+        }
+        if (!intern) {
+            DCHK(d, hipMemcpyAsync(out_key_offsets, koff, 8 * (size_t)(n + 1), hipMemcpyDeviceToHost, s));
+            DCHK(d, hipMemcpyAsync(out_key_lengths, klen, 4 * (size_t)n, hipMemcpyDeviceToHost, s));
+        }
+    }
+    if (!intern) {
+        *out_nbytes = total;
+        if (total > cap_bytes) {
+            if (host) DCHK(d, hipStreamSynchronize(s));
+            timed(ms, 0);
+            return d->fail(FG_EFULL, who + ": the key rows take " + std::to_string(total) + " bytes, out_key_bytes holds " +
+                                         std::to_string(cap_bytes));
+        }
+    }
+    // 2) the key rows: every row is good and the buffer holds `total` bytes (a key row has at least 16)
+    uint8_t* kbytes = out_key_bytes;
+    if (host || intern) {
+        DCHK(d, d->pj_kbytes.ensure((size_t)total, s));
+        kbytes = d->pj_kbytes.as<uint8_t>();
+    }
+    if (d->timing) DCHK(d, hipEventRecord(d->ev[15], s));
+    DCHK(d, keyproj_write(s, a, koff, reinterpret_cast<uint64_t*>(kbytes), total >> 3));
+    if (d->timing) DCHK(d, hipEventRecord(d->ev[16], s));
+    if (host && !intern) DCHK(d, hipMemcpyAsync(out_key_bytes, kbytes, (size_t)total, hipMemcpyDeviceToHost, s));
+    DCHK(d, hipStreamSynchronize(s));
+    if (d->timing) {
+        float ms2 = 0.f;
+        DCHK(d, hipEventElapsedTime(&ms2, d->ev[15], d->ev[16]));
+        ms += ms2;
+    }
+    timed(ms, total);
+    if (!intern) return FG_OK;
+    // 3) the key rows interned where they lie
+    int64_t* ids = out_id;
+    int32_t* kg = out_kg;
+    if (host) {
+        DCHK(d, d->pj_ids.ensure(8 * (size_t)n, s));
+        ids = d->pj_ids.as<int64_t>();
+        if (out_kg) {
+            DCHK(d, d->pj_kg.ensure(4 * (size_t)n, s));
+            kg = d->pj_kg.as<int32_t>();
+        }
+    }
+    if (int rc1 = intern_begin(d, FG_DEVICE, n, kbytes, total, koff, klen, ids, kg)) return rc1;
+    if (int rc2 = intern_finish(d)) return rc2;
+    if (host) {
+        DCHK(d, hipMemcpy(out_id, ids, 8 * (size_t)n, hipMemcpyDeviceToHost));
+        if (out_kg) DCHK(d, hipMemcpy(out_kg, kg, 4 * (size_t)n, hipMemcpyDeviceToHost));
+    }
+    return FG_OK;
+}
+
+int fg_key_dict_project(fg_key_dict* d, int32_t location, int64_t n, const uint8_t* bytes, int64_t nbytes,
+                        const int64_t* offsets, const int32_t* lengths, const fg_row_projection* proj, uint8_t* out_key_bytes,
+                        int64_t cap_bytes, int64_t* out_key_offsets, int32_t* out_key_lengths, int64_t* const* out_cols,
+                        uint8_t* const* out_col_null, int64_t* out_nbytes) {
+    return project_impl(d, false, location, n, bytes, nbytes, offsets, lengths, proj, out_key_bytes, cap_bytes,
+                        out_key_offsets, out_key_lengths, out_cols, out_col_null, out_nbytes, nullptr, nullptr);
+}
+
+int fg_key_dict_intern_fields(fg_key_dict* d, int32_t location, int64_t n, const uint8_t* bytes, int64_t nbytes,
+                              const int64_t* offsets, const int32_t* lengths, const fg_row_projection* proj, int64_t* out_id,
+                              int32_t* out_kg, int64_t* const* out_cols, uint8_t* const* out_col_null) {
+    return project_impl(d, true, location, n, bytes, nbytes, offsets, lengths, proj, nullptr, 0, nullptr, nullptr, out_cols,
+                        out_col_null, nullptr, out_id, out_kg);
+}
+
 int fg_key_dict_get_stats(fg_key_dict* d, fg_key_dict_stats* out) {
     if (!d || !out) return FG_EINVAL;
     out->live = d->live();
@@ -1622,6 +1775,7 @@ int fg_key_dict_set_timing(fg_key_dict* d, int32_t on) {
         std::snprintf(d->kstat[2].name, sizeof d->kstat[2].name, "dict_rows");
         std::snprintf(d->kstat[3].name, sizeof d->kstat[3].name, "dict_retain");
         std::snprintf(d->kstat[4].name, sizeof d->kstat[4].name, "dict_rebuild");
+        std::snprintf(d->kstat[5].name, sizeof d->kstat[5].name, "dict_project");
     }
     d->timing = on != 0;
     return FG_OK;
@@ -1629,7 +1783,7 @@ int fg_key_dict_set_timing(fg_key_dict* d, int32_t on) {
 
 int fg_key_dict_kernel_stats(fg_key_dict* d, fg_kernel_stat* out, int32_t max, int32_t* count) {
     if (!d || !count || (max > 0 && !out)) return FG_EINVAL;
-    *count = d->ev[0] ? 5 : 0;
+    *count = d->ev[0] ? (d->projected ? 6 : 5) : 0;   // ("dict_project" only once the dictionary has projected)
     for (int i = 0; i < *count && i < max; i++) out[i] = d->kstat[i];
     return FG_OK;
 }

@@ -10,6 +10,9 @@ GPU (equal rows -> equal ids, exact), which the window operators aggregate as BI
 `retain` keeps the ids that still hold state and retires the rest (their ordinals are reused);
 `rows` gathers the packed key rows of ids on the GPU (fired rows, checkpoints; `lookup` is its
 list-of-bytes form) and `reintern` carries ids from one dictionary into another (rescale).
+`project` / `intern_fields` are the key selector itself on the GPU: packed BinaryRowData records
+in, their key rows (or ids) and the rowtime / value columns out (`RowProjection` says which fields;
+`project_key_row` is the pure-Python reference of one row).
 `key_row` / `decode_key_row` write and read key rows the way BinaryRowWriter does (writer/BinaryRowWriter.java, AbstractBinaryWriter.java:
 81-105,280-330: STRING of <= 7 bytes inline in its 8-byte slot as 0x80|len in the top byte,
 longer ones in the variable part, 8-byte aligned, the slot holding offset << 32 | length).
@@ -33,8 +36,8 @@ def dict_kg_bits(max_parallelism: int) -> int:
 
 
 def key_row(fields, types, row_kind: int = 0) -> bytes:
-    """One BinaryRowData key row. types[i] in {"string", "bigint", "int", "double", "boolean"};
-    a None field is NULL (null bit set, slot zero: BinaryRowWriter.setNullAt)."""
+    """One BinaryRowData key row. types[i] in {"string", "bigint", "int", "double", "boolean", "float",
+    "smallint", "tinyint"}; a None field is NULL (null bit set, slot zero: BinaryRowWriter.setNullAt)."""
     arity = len(fields)
     w = bit_set_width(arity)
     fixed = bytearray(w + 8 * arity)
@@ -63,6 +66,12 @@ def key_row(fields, types, row_kind: int = 0) -> bytes:
             fixed[slot:slot + 8] = struct.pack("<d", float(v))
         elif t == "boolean":
             fixed[slot] = 1 if v else 0
+        elif t == "float":
+            fixed[slot:slot + 4] = struct.pack("<f", float(v))
+        elif t == "smallint":
+            fixed[slot:slot + 2] = struct.pack("<h", int(v))
+        elif t == "tinyint":
+            fixed[slot:slot + 1] = struct.pack("<b", int(v))
         else:
             raise ValueError(f"unsupported key field type {t!r}")
     return bytes(fixed + var)
@@ -95,7 +104,82 @@ def decode_key_row(row: bytes, types):
             out.append(struct.unpack("<d", slot)[0])
         elif t == "boolean":
             out.append(bool(slot[0]))
+        elif t == "float":
+            out.append(struct.unpack("<f", slot[:4])[0])
+        elif t == "smallint":
+            out.append(struct.unpack("<h", slot[:2])[0])
+        elif t == "tinyint":
+            out.append(struct.unpack("<b", slot[:1])[0])
     return tuple(out)
+
+
+_KIND_OF_TYPE = {"string": L.FIELD_VAR, "bigint": L.FIELD_FIX8, "double": L.FIELD_FIX8, "int": L.FIELD_FIX4,
+                 "float": L.FIELD_FIX4, "smallint": L.FIELD_FIX2, "tinyint": L.FIELD_FIX1, "boolean": L.FIELD_FIX1}
+_TYPE_OF_KIND = {L.FIELD_VAR: "string", L.FIELD_FIX8: "bigint", L.FIELD_FIX4: "int", L.FIELD_FIX2: "smallint",
+                 L.FIELD_FIX1: "tinyint"}
+
+
+class RowProjection:
+    """fg_row_projection: which fields of an input row of `arity` fields make its key row
+    (key_fields, in key order; key_kinds their fg_field_kind -- L.FIELD_* or a key_row type name)
+    and which 8-byte fields come out as columns (col_fields: rowtime, value)."""
+
+    def __init__(self, arity, key_fields, key_kinds, col_fields=()):
+        self.arity = int(arity)
+        self.key_fields = tuple(int(f) for f in key_fields)
+        self.key_kinds = tuple(_KIND_OF_TYPE[k] if isinstance(k, str) else int(k) for k in key_kinds)
+        self.col_fields = tuple(int(f) for f in col_fields)
+        if len(self.key_fields) != len(self.key_kinds):
+            raise ValueError("one kind per key field expected")
+        if len(self.key_fields) > L.PROJ_MAX_KEY_FIELDS or len(self.col_fields) > L.PROJ_MAX_COLS:
+            raise ValueError(f"at most {L.PROJ_MAX_KEY_FIELDS} key fields and {L.PROJ_MAX_COLS} columns")
+
+    def struct(self) -> "L.FgRowProjection":
+        p = L.FgRowProjection()
+        p.arity = self.arity
+        p.n_key_fields = len(self.key_fields)
+        p.n_cols = len(self.col_fields)
+        for f, (field, kind) in enumerate(zip(self.key_fields, self.key_kinds)):
+            p.key_field[f] = field
+            p.key_kind[f] = kind
+        for c, field in enumerate(self.col_fields):
+            p.col_field[c] = field
+        return p
+
+
+def project_key_row(row: bytes, proj: RowProjection) -> bytes:
+    """The key row fg_key_dict_project writes for one input row (a pure-Python reference): the key
+    fields decoded by the rules of include/flinkgpu.h and written with key_row. A bad row raises
+    ValueError."""
+    w = bit_set_width(proj.arity)
+    fixed = w + 8 * proj.arity
+    if len(row) % 8 or len(row) < fixed:
+        raise ValueError("a row shorter than its fixed-length part, or not a multiple of 8 bytes")
+    fields, types = [], []
+    for field, kind in zip(proj.key_fields, proj.key_kinds):
+        types.append(_TYPE_OF_KIND[kind])
+        b = HEADER_SIZE_IN_BITS + field
+        if row[b >> 3] >> (b & 7) & 1:
+            fields.append(None)
+            continue
+        slot = row[w + 8 * field: w + 8 * field + 8]
+        word = int.from_bytes(slot, "little")
+        if kind != L.FIELD_VAR:
+            fields.append(int.from_bytes(slot[:kind], "little", signed=True))
+        elif word >> 63:
+            n = (word >> 56) & 0x7F
+            if n > 7:
+                raise ValueError("an inline field longer than 7 bytes")
+            fields.append(slot[:n])
+        else:
+            off, n = word >> 32, word & 0xFFFFFFFF
+            if off % 8 or off < fixed or off + n > len(row):
+                raise ValueError("a variable-length field outside its row")
+            fields.append(row[off:off + n])
+    out = key_row(fields, types)
+    if len(out) > (1 << 24) - 4:
+        raise ValueError("a key row above 2^24 - 4 bytes")
+    return out
 
 
 def pack_key_rows(rows):
@@ -285,6 +369,77 @@ class KeyDictionary:
         self._check(rc)
         return buf[:int(nbytes.value)], off, ln
 
+    def _records(self, packed_rows, proj):
+        """the inputs of project / intern_fields: (device?, n, records, struct, ptr, alloc, out_cols,
+        out_nulls, their pointer arrays); device records order the dictionary's stream after their
+        producer"""
+        buf, off, ln = packed_rows
+        dev = hasattr(buf, "data_ptr")
+        if dev:
+            import torch
+            buf, off, ln = buf.contiguous(), off.to(torch.int64).contiguous(), ln.to(torch.int32).contiguous()
+            ext = self.__dict__.get("_ext_stream")
+            if ext is None or ext.device != buf.device:
+                ext = self._ext_stream = torch.cuda.ExternalStream(self._lib.fg_key_dict_stream(self._h),
+                                                                   device=buf.device)
+            ext.wait_stream(torch.cuda.current_stream(buf.device))
+            kinds = {"u8": torch.uint8, "i32": torch.int32, "i64": torch.int64}
+            alloc = lambda m, kind: torch.empty(m, dtype=kinds[kind], device=buf.device)   # noqa: E731
+            ptr = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
+            nbytes = buf.numel()
+        else:
+            buf = np.ascontiguousarray(buf, dtype=np.uint8)
+            off = np.ascontiguousarray(off, dtype=np.int64)
+            ln = np.ascontiguousarray(ln, dtype=np.int32)
+            kinds = {"u8": np.uint8, "i32": np.int32, "i64": np.int64}
+            alloc = lambda m, kind: np.empty(m, dtype=kinds[kind])   # noqa: E731
+            ptr = lambda a: C.c_void_p(a.ctypes.data)   # noqa: E731
+            nbytes = buf.size
+        n = len(ln)
+        cols = [alloc(n, "i64") for _ in proj.col_fields]
+        nulls = [alloc(n, "u8") for _ in proj.col_fields]
+        k = max(len(cols), 1)
+        pc = (C.c_void_p * k)(*[ptr(c) for c in cols])
+        pn = (C.c_void_p * k)(*[ptr(c) for c in nulls])
+        return dev, n, (buf, nbytes, off, ln), proj.struct(), ptr, alloc, cols, nulls, pc, pn
+
+    def project(self, packed_rows, proj: RowProjection):
+        """fg_key_dict_project: the key rows of packed BinaryRowData records packed_rows=(bytes u8[],
+        offsets i64[n], lengths i32[n]), projected on the GPU: (bytes u8[nbytes], offsets i64[n + 1],
+        lengths i32[n], cols, col_nulls) -- the key rows in the layout intern() reads, and per
+        proj.col_fields an int64 column and its uint8 NULL column. Numpy in gives numpy out; device
+        tensors in give device tensors out (no byte touches the host). At most two C calls: a guess
+        of 32 bytes per key row, one retry at the exact size. A bad row raises WindowSpecError."""
+        dev, n, (buf, nbytes, off, ln), ps, ptr, alloc, cols, nulls, pc, pn = self._records(packed_rows, proj)
+        koff = alloc(n + 1, "i64")
+        klen = alloc(n, "i32")
+        if n == 0:
+            koff[:] = 0
+            return alloc(0, "u8"), koff, klen, cols, nulls
+        total = C.c_int64()
+        cap = 32 * n
+        for _ in range(2):
+            kbuf = alloc(max(cap, 8), "u8")
+            rc = self._lib.fg_key_dict_project(self._h, L.DEVICE if dev else L.HOST, n, ptr(buf), nbytes, ptr(off), ptr(ln),
+                                               C.byref(ps), ptr(kbuf), cap, ptr(koff), ptr(klen), pc, pn, C.byref(total))
+            if rc != L.FG_EFULL:
+                break
+            cap = int(total.value)
+        self._check(rc)
+        return kbuf[:int(total.value)], koff, klen, cols, nulls
+
+    def intern_fields(self, packed_rows, proj: RowProjection, key_groups=True):
+        """fg_key_dict_intern_fields: records in, ids out -- project() into the dictionary's device
+        scratch and intern() of those key rows in one call: (ids i64[n], key_groups i32[n] or None,
+        cols, col_nulls), numpy or device tensors like the input."""
+        dev, n, (buf, nbytes, off, ln), ps, ptr, alloc, cols, nulls, pc, pn = self._records(packed_rows, proj)
+        ids = alloc(n, "i64")
+        kg = alloc(n, "i32") if key_groups else None
+        self._check(self._lib.fg_key_dict_intern_fields(self._h, L.DEVICE if dev else L.HOST, n, ptr(buf), nbytes, ptr(off),
+                                                        ptr(ln), C.byref(ps), ptr(ids),
+                                                        ptr(kg) if key_groups else None, pc, pn))
+        return ids, kg, cols, nulls
+
     def lookup(self, ids):
         """Key rows (bytes) of the ids (host)."""
         buf, off, ln = self.rows(np.ascontiguousarray(ids, dtype=np.int64))
@@ -340,7 +495,7 @@ class KeyDictionary:
 
     def kernel_stats(self) -> dict:
         """{"dict_probe" | "dict_assign" | "dict_rows" | "dict_retain" | "dict_rebuild": dict(launches,
-        total_ms, records, rows)}."""
+        total_ms, records, rows)}, and "dict_project" once the dictionary has projected."""
         arr = (L.FgKernelStat * 8)()
         n = C.c_int32()
         self._check(self._lib.fg_key_dict_kernel_stats(self._h, arr, 8, C.byref(n)))

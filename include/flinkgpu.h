@@ -868,6 +868,100 @@ int  fg_key_dict_rows(fg_key_dict* d, int32_t location, int64_t n, const int64_t
                       uint8_t* out_bytes, int64_t cap_bytes,
                       int64_t* out_offsets /* [n + 1] */, int32_t* out_lengths /* [n] */,
                       int64_t* out_nbytes /* always a host pointer */);
+/* The key selector on the GPU (ABI 16, added): the key rows of n packed BinaryRowData records,
+ * projected the way the reference's BinaryRowDataKeySelector.getKey does (the generated projection
+ * writing through BinaryRowWriter, BinaryRowDataKeySelector.java:43-50), plus up to
+ * FG_PROJ_MAX_COLS 8-byte fields copied out as columns (rowtime, value) -- the way into the
+ * dictionary for a GROUP BY on a STRING column, several key columns or a nullable key, with no
+ * per-record host work. Input records are whole rows, fixed-length part and variable-length part:
+ *   row i = bytes[offsets[i], offsets[i] + lengths[i]) (nbytes = the buffer's size) -- the layout
+ *   fg_key_dict_intern reads, except that every offset and length is a multiple of 8 (a
+ *   BinaryRowData's size always is); proj->arity is the rows' field count.
+ * location is FG_HOST or FG_DEVICE and covers every pointer except proj, the two pointer arrays
+ * out_cols / out_col_null (host arrays of pointers at `location`) and out_nbytes (always a host
+ * pointer). FG_HOST inputs (pageable or pinned) are copied up on the dictionary's stream and the
+ * host outputs are complete when the call returns; FG_DEVICE pointers are read and written on the
+ * dictionary's stream (fg_key_dict_stream) under the ordering rule of fg_key_dict_intern, complete
+ * when the call returns; device bytes and out_key_bytes are 8-byte aligned. The dictionary lends
+ * its stream, scratch, timing and error text: fg_key_dict_project does not modify it.
+ * The key row of an input row is byte-exact (little endian, k = n_key_fields):
+ *   header     8 bytes of bit set (((k + 71) / 64) * 8): byte 0 is RowKind INSERT = 0 whatever the
+ *              input row's RowKind; bit 8 + f is set iff input field key_field[f] is NULL, and its
+ *              slot is then eight zero bytes (BinaryRowWriter.setNullAt);
+ *   slots      8 bytes per key field. FG_FIELD_FIXw copies the low w bytes of the input slot and
+ *              zeroes the rest (canonical whatever the input slot holds there);
+ *   FG_FIELD_VAR  is decoded from the input slot either way -- top bit set: inline, len = bits
+ *              56..62, data in the low bytes; otherwise offset << 32 | len, the offset from the
+ *              row's start -- and re-encoded as BinaryRowWriter.writeString / writeBytes does
+ *              (AbstractBinaryWriter.java:81-105,280-330): len <= 7 inline (0x80 | len in the top
+ *              byte, unused bytes zero), also when the input kept it in its variable part; a longer
+ *              one in the key row's variable part, the fields in key-field order, each zero-padded
+ *              to 8 (its last word masked by its length, not trusted from the input), the slot
+ *              holding key_row_offset << 32 | len, the first offset being 8 * (k + 1).
+ *   out_key_lengths[i] is the row's length (a multiple of 8); out_key_offsets has n + 1 entries,
+ *   the prefix of the lengths: [0] = 0, [n] = *out_nbytes; rows are packed back to back. The
+ *   output is valid input to fg_key_dict_intern, on the device or on the host.
+ * Columns: out_cols[c][i] = the 8 bytes of field col_field[c], 0 when it is NULL; out_col_null[c][i]
+ * = 1 for NULL, 0 otherwise, where that pointer is non-NULL (out_col_null itself may be NULL).
+ * A row is bad if its offset or length is negative or not a multiple of 8, offsets[i] + lengths[i] >
+ * nbytes, lengths[i] is smaller than the fixed-length part of `arity` fields, a non-NULL
+ * FG_FIELD_VAR key field is inline with a length above 7, lies in the variable part at an offset
+ * that is not a multiple of 8 or is below the fixed-length part, or has offset + len beyond the
+ * row's length, its key row would exceed the intern's limit of 2^24 - 4 bytes, or a column field
+ * is NULL while its out_col_null[c] is NULL (the fg_add_rows rule: a NULL key or rowtime is
+ * FG_EINVAL). Bad rows are found in the length pass; no byte is read through an unchecked offset.
+ * Returns
+ *   FG_EFULL   (_project) *out_nbytes > cap_bytes: out_key_offsets, out_key_lengths, the columns
+ *              and *out_nbytes are complete, out_key_bytes is untouched. out_key_bytes NULL with
+ *              cap_bytes 0 is the sizing call;
+ *   FG_EINVAL  before any device work: a NULL d or proj; an unknown location; n < 0 or n > 2^31 - 1;
+ *              nbytes < 0; n > 0 with a NULL bytes / offsets / lengths / out_key_offsets /
+ *              out_key_lengths / out_nbytes (_project) or a NULL out_id (_intern_fields); arity
+ *              outside 1..32767, n_key_fields outside 1..FG_PROJ_MAX_KEY_FIELDS, n_cols outside
+ *              0..FG_PROJ_MAX_COLS; a field index outside 0..arity - 1; an unknown kind; n > 0 and
+ *              n_cols > 0 with a NULL out_cols or a NULL entry; cap_bytes < 0, or cap_bytes > 0 with a NULL
+ *              out_key_bytes; misaligned device bytes or out_key_bytes;
+ *   FG_EINVAL  after the length pass (one host read of {total, bad rows, lowest bad index}, as
+ *              fg_key_dict_rows): any bad row -- the message gives how many and the lowest index; no
+ *              key byte is written and nothing is interned;
+ *   FG_ESTATE  while an async intern is pending.
+ * n == 0: FG_OK, *out_nbytes = 0, out_key_offsets[0] = 0 where non-NULL, no kernel runs. The
+ * dictionary stays usable after every error. A long string is copied by a whole workgroup.
+ * fg_key_dict_set_timing class "dict_project": all of a projection's kernels, records = the input
+ * rows, rows = the key bytes written; listed only once the dictionary has projected. */
+enum fg_field_kind { FG_FIELD_FIX1 = 1,   /* BOOLEAN, TINYINT */
+                     FG_FIELD_FIX2 = 2,   /* SMALLINT */
+                     FG_FIELD_FIX4 = 4,   /* INT, DATE, TIME, FLOAT */
+                     FG_FIELD_FIX8 = 8,   /* BIGINT, DOUBLE, TIMESTAMP(<=3) compact */
+                     FG_FIELD_VAR  = 16 };/* CHAR / VARCHAR / STRING / BINARY / VARBINARY */
+#define FG_PROJ_MAX_KEY_FIELDS 8
+#define FG_PROJ_MAX_COLS 4
+typedef struct fg_row_projection {
+    int32_t arity;                                /* fields of an input row, 1 .. 32767 */
+    int32_t n_key_fields;                         /* 1 .. FG_PROJ_MAX_KEY_FIELDS */
+    int32_t key_field[FG_PROJ_MAX_KEY_FIELDS];    /* input field of key field f (any order, repeats allowed) */
+    int32_t key_kind[FG_PROJ_MAX_KEY_FIELDS];     /* fg_field_kind */
+    int32_t n_cols;                               /* 0 .. FG_PROJ_MAX_COLS */
+    int32_t col_field[FG_PROJ_MAX_COLS];          /* 8-byte input fields copied out as columns (rowtime, value) */
+} fg_row_projection;
+int  fg_key_dict_project(fg_key_dict* d, int32_t location, int64_t n,
+                         const uint8_t* bytes, int64_t nbytes, const int64_t* offsets, const int32_t* lengths,
+                         const fg_row_projection* proj,
+                         uint8_t* out_key_bytes, int64_t cap_bytes,
+                         int64_t* out_key_offsets /* [n + 1] */, int32_t* out_key_lengths /* [n] */,
+                         int64_t* const* out_cols /* [n_cols] columns of n, may be NULL when n_cols == 0 */,
+                         uint8_t* const* out_col_null /* [n_cols], each entry may be NULL */,
+                         int64_t* out_nbytes /* always a host pointer */);
+/* fg_key_dict_project into dictionary-owned device scratch, then fg_key_dict_intern of those rows:
+ * records in, ids (and columns) out. out_id[n] are the ids fg_key_dict_intern returns for the same
+ * key rows (equal keys give equal ids; a key first seen through either entry point is found by the
+ * other), out_kg[n] (optional) their key groups. Arguments, bad rows and errors as above; the
+ * scratch grows to the largest call and is freed at fg_key_dict_close. There is no async form. */
+int  fg_key_dict_intern_fields(fg_key_dict* d, int32_t location, int64_t n,
+                               const uint8_t* bytes, int64_t nbytes, const int64_t* offsets, const int32_t* lengths,
+                               const fg_row_projection* proj,
+                               int64_t* out_id, int32_t* out_kg /* optional */,
+                               int64_t* const* out_cols, uint8_t* const* out_col_null);
 /* fg_partition_columns_by_owner for rows keyed by ids of dictionary d (cols[0] = ids; owner from the key
  * group an id carries, FG_KEYHASH_DICT_ID, under d's max parallelism), plus what the owner needs to know
  * the keys: the key rows of the grouped ids, packed back to back in the grouped order, each zero-padded

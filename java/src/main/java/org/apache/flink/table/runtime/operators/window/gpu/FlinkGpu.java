@@ -280,6 +280,52 @@ public final class FlinkGpu {
             ByteBuffer outOffsets,
             ByteBuffer outLengths);
 
+    /** fg_field_kind: how a key field is stored in its 8-byte slot (the bytes copied; VAR: CHAR / VARCHAR / BINARY). */
+    public static final int FIELD_FIX1 = 1, FIELD_FIX2 = 2, FIELD_FIX4 = 4, FIELD_FIX8 = 8, FIELD_VAR = 16;
+
+    /**
+     * fg_key_dict_project (FG_HOST): the key rows of n serialized records (whole BinaryRowData rows:
+     * record i at offsets[i], lengths[i] bytes, both multiples of 8), projected on the GPU the way
+     * BinaryRowDataKeySelector.getKey projects them. projection = {arity, nKeyFields, nCols,
+     * keyField[0], keyKind[0], ..., colField[0], ...}; outCols holds nCols columns of n longs back to
+     * back (the 8 bytes of each column field, 0 for NULL), outColNull (may be null) nCols columns of
+     * n bytes. The key rows come out as dictIntern reads them (outKeyOffsets holds n + 1 longs).
+     * Returns the bytes they take; a result above capBytes means outKeyBytes was too small and is
+     * untouched: grow it and call again.
+     */
+    public static native long dictProject(
+            long d,
+            ByteBuffer rows,
+            long nbytes,
+            ByteBuffer offsets,
+            ByteBuffer lengths,
+            int n,
+            long[] projection,
+            ByteBuffer outKeyBytes,
+            long capBytes,
+            ByteBuffer outKeyOffsets,
+            ByteBuffer outKeyLengths,
+            ByteBuffer outCols,
+            ByteBuffer outColNull);
+
+    /**
+     * fg_key_dict_intern_fields (FG_HOST): dictProject into the dictionary's device scratch and
+     * dictIntern of those key rows in one call -- serialized records in, ids (and columns) out;
+     * outKeyGroups and outColNull may be null.
+     */
+    public static native void dictInternFields(
+            long d,
+            ByteBuffer rows,
+            long nbytes,
+            ByteBuffer offsets,
+            ByteBuffer lengths,
+            int n,
+            long[] projection,
+            ByteBuffer outIds,
+            ByteBuffer outKeyGroups,
+            ByteBuffer outCols,
+            ByteBuffer outColNull);
+
     /**
      * fg_key_dict_retain (one FG_HOST set): keep exactly ids[0 .. n), retire every other entry and
      * reuse its ordinal for later interns; n == 0 empties the dictionary. Returns the 8 words of

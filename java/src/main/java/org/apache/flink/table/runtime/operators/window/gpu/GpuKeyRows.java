@@ -106,6 +106,32 @@ final class GpuKeyRows implements AutoCloseable {
         bytes = 0;
     }
 
+    /**
+     * The key selector on the GPU: count serialized records (whole BinaryRowData rows packed in rows[0 ..
+     * nbytes), record i at recOffsets[i] with recLengths[i] bytes) -> their ids in keys[0 .. count) and the
+     * projection's 8-byte columns (rowtime, value) in outCols / outColNull, by ONE dictInternFields call: the
+     * GPU projects the key rows (what keySelector.getKey + add would build one record at a time) and interns
+     * them. projection as FlinkGpu.dictProject takes it. Not for a BIGINT key (fg_add_rows reads those rows).
+     */
+    void internFields(
+            ByteBuffer rows,
+            long nbytes,
+            ByteBuffer recOffsets,
+            ByteBuffer recLengths,
+            int count,
+            long[] projection,
+            ByteBuffer keys,
+            ByteBuffer outCols,
+            ByteBuffer outColNull) {
+        if (bigint) {
+            throw new IllegalStateException("internFields: a BIGINT key needs no dictionary");
+        }
+        if (count == 0) {
+            return;
+        }
+        FlinkGpu.dictInternFields(dict, rows, nbytes, recOffsets, recLengths, count, projection, keys, null, outCols, outColNull);
+    }
+
     /** the key rows of ids keys[0 .. count) (one dictRows into the reused buffers) */
     RowData[] rows(ByteBuffer keys, int count) {
         RowData[] out = new RowData[count];

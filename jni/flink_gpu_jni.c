@@ -659,6 +659,90 @@ JNIEXPORT jlong JNICALL FN(dictRows)(JNIEnv* env, jclass cls, jlong dp, jobject 
     return nbytes;
 }
 
+/* The projection of dictProject / dictInternFields as a long[] (like firedPacked's shape array):
+ * {arity, nKeyFields, nCols, keyField[0], keyKind[0], ..., colField[0], ...}. 0 on success. */
+static int projection_of(JNIEnv* env, jlongArray shape, fg_row_projection* p) {
+    memset(p, 0, sizeof *p);
+    const jsize len = shape ? (*env)->GetArrayLength(env, shape) : 0;
+    jlong* v = len >= 3 ? (*env)->GetLongArrayElements(env, shape, NULL) : NULL;
+    int ok = v && v[1] >= 0 && v[1] <= FG_PROJ_MAX_KEY_FIELDS && v[2] >= 0 && v[2] <= FG_PROJ_MAX_COLS &&
+             len >= 3 + 2 * v[1] + v[2];
+    if (ok) {
+        p->arity = (int32_t)v[0];
+        p->n_key_fields = (int32_t)v[1];
+        p->n_cols = (int32_t)v[2];
+        for (int f = 0; f < p->n_key_fields; f++) {
+            p->key_field[f] = (int32_t)v[3 + 2 * f];
+            p->key_kind[f] = (int32_t)v[4 + 2 * f];
+        }
+        for (int c = 0; c < p->n_cols; c++) p->col_field[c] = (int32_t)v[3 + 2 * p->n_key_fields + c];
+    }
+    if (v) (*env)->ReleaseLongArrayElements(env, shape, v, JNI_ABORT);
+    if (!ok) throw_code(env, FG_EINVAL, "projection: {arity, nKeyFields <= 8, nCols <= 4, (field, kind) pairs, column fields}");
+    return ok ? 0 : 1;
+}
+
+/* column c of outCols (n longs each, back to back) and of outColNull (n bytes each; may be null) */
+static void projection_columns(const fg_row_projection* p, int64_t n, int64_t* cols, uint8_t* nulls,
+                               int64_t* pc[FG_PROJ_MAX_COLS], uint8_t* pn[FG_PROJ_MAX_COLS]) {
+    for (int c = 0; c < FG_PROJ_MAX_COLS; c++) {
+        pc[c] = c < p->n_cols && cols ? cols + (int64_t)c * n : NULL;
+        pn[c] = c < p->n_cols && nulls ? nulls + (int64_t)c * n : NULL;
+    }
+}
+
+/* long dictProject(long d, ByteBuffer rows, long nbytes, ByteBuffer offsets, ByteBuffer lengths, int n, long[] projection,
+ *                  ByteBuffer outKeyBytes, long capBytes, ByteBuffer outKeyOffsets, ByteBuffer outKeyLengths,
+ *                  ByteBuffer outCols, ByteBuffer outColNull) -- fg_key_dict_project (FG_HOST): the key rows of n
+ * serialized records, projected on the GPU. outCols holds nCols columns of n longs back to back, outColNull (may be
+ * null) nCols columns of n bytes. Returns the bytes the key rows take; as with dictRows FG_EFULL is no exception: a
+ * result above capBytes means outKeyBytes was too small and is untouched (everything else is complete). */
+JNIEXPORT jlong JNICALL FN(dictProject)(JNIEnv* env, jclass cls, jlong dp, jobject rows, jlong nbytes, jobject offsets,
+                                        jobject lengths, jint n, jlongArray projection, jobject outKeyBytes, jlong capBytes,
+                                        jobject outKeyOffsets, jobject outKeyLengths, jobject outCols, jobject outColNull) {
+    (void)cls;
+    fg_key_dict* d = (fg_key_dict*)(intptr_t)dp;
+    fg_row_projection p;
+    if (projection_of(env, projection, &p)) return 0;
+    const uint8_t* r = (const uint8_t*)addr(env, rows);
+    const int64_t* o = (const int64_t*)addr(env, offsets);
+    const int32_t* l = (const int32_t*)addr(env, lengths);
+    uint8_t* kb = (uint8_t*)addr(env, outKeyBytes);
+    int64_t* ko = (int64_t*)addr(env, outKeyOffsets);
+    int32_t* kl = (int32_t*)addr(env, outKeyLengths);
+    int64_t* pc[FG_PROJ_MAX_COLS];
+    uint8_t* pn[FG_PROJ_MAX_COLS];
+    projection_columns(&p, n, (int64_t*)addr(env, outCols), (uint8_t*)addr(env, outColNull), pc, pn);
+    int64_t total = 0;
+    if ((*env)->ExceptionCheck(env)) return 0;
+    const int rc = fg_key_dict_project(d, FG_HOST, n, r, nbytes, o, l, &p, kb, capBytes, ko, kl, pc, pn, &total);
+    if (rc != FG_EFULL) dcheck(env, d, rc);
+    return total;
+}
+
+/* void dictInternFields(long d, ByteBuffer rows, long nbytes, ByteBuffer offsets, ByteBuffer lengths, int n,
+ *                       long[] projection, ByteBuffer outIds, ByteBuffer outKeyGroups, ByteBuffer outCols,
+ *                       ByteBuffer outColNull) -- fg_key_dict_intern_fields (FG_HOST): serialized records in, ids and
+ * columns out; outKeyGroups and outColNull may be null */
+JNIEXPORT void JNICALL FN(dictInternFields)(JNIEnv* env, jclass cls, jlong dp, jobject rows, jlong nbytes, jobject offsets,
+                                            jobject lengths, jint n, jlongArray projection, jobject outIds, jobject outKg,
+                                            jobject outCols, jobject outColNull) {
+    (void)cls;
+    fg_key_dict* d = (fg_key_dict*)(intptr_t)dp;
+    fg_row_projection p;
+    if (projection_of(env, projection, &p)) return;
+    const uint8_t* r = (const uint8_t*)addr(env, rows);
+    const int64_t* o = (const int64_t*)addr(env, offsets);
+    const int32_t* l = (const int32_t*)addr(env, lengths);
+    int64_t* ids = (int64_t*)addr(env, outIds);
+    int32_t* kg = (int32_t*)addr(env, outKg);
+    int64_t* pc[FG_PROJ_MAX_COLS];
+    uint8_t* pn[FG_PROJ_MAX_COLS];
+    projection_columns(&p, n, (int64_t*)addr(env, outCols), (uint8_t*)addr(env, outColNull), pc, pn);
+    if ((*env)->ExceptionCheck(env)) return;
+    dcheck(env, d, fg_key_dict_intern_fields(d, FG_HOST, n, r, nbytes, o, l, &p, ids, kg, pc, pn));
+}
+
 static jlongArray dict_stats_array(JNIEnv* env, const fg_key_dict_stats* st) {
     const jlong v[8] = {st->live, st->issued, st->free_ordinals, st->arena_bytes, st->table_slots, st->side_rows,
                         st->retired_total, st->reserved0};
